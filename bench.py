@@ -12,6 +12,13 @@ kernel, position advance — hipGraph-replayed.
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 the
 driver launches one rank per GPU via torch.distributed.run. Rank 0 prints
 one JSON line with the whole-job aggregate.
+
+A plain run does only what the headline needs: set up, warm up, time the
+K steps, print the line. `--full` adds the second half of the BASELINE
+metric (p50 agent tool-turn latency, measured after the timed region).
+`--dump-outputs DIR` writes the token ids the run produced and the last
+timed step's logits as DIR/<name>.npy (seeds are fixed, so the same
+arguments give the same inputs and two builds compare output for output).
 """
 
 from __future__ import annotations
@@ -23,6 +30,39 @@ import sys
 import time
 
 import torch
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20      # --dump-outputs writes at most this
+
+
+def _record_logits(model, sink: dict) -> None:
+    """Keep a reference to the logits tensor each decode forward returns.
+    Installed BEFORE graph capture: the captured step then writes its
+    logits into a tensor we hold, so after the last replay it carries the
+    last timed step's logits (the engine itself drops them after sampling)."""
+    for name in ("forward_decode", "forward_decode_stream"):
+        orig = getattr(model, name)
+
+        def wrapped(*a, _orig=orig, **k):
+            sink["logits"] = _orig(*a, **k)
+            return sink["logits"]
+        setattr(model, name, wrapped)
+
+
+def _dump_outputs(out_dir: str, arrays: dict, rank: int) -> None:
+    """Write each array as <name>.npy (rank > 0: <name>.rank<r>.npy). An
+    array over its share of the byte budget is cut to a fixed, seeded
+    sample of its flattened elements (same indices every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(
+                a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        suffix = f".rank{rank}" if rank else ""
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 def main() -> int:
@@ -46,6 +86,16 @@ def main() -> int:
                    help="tensor-parallel degree: the W ranks run ONE agent "
                         "sharded over RCCL/xGMI instead of W independent "
                         "agents (requires world_size == tp)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure p50 agent tool-turn latency after the "
+                        "timed steps (several seconds of extra GPU work; "
+                        "reported under config.tool_turn_*)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the decode outputs "
+                        "(tokens.npy: every token id the run produced, "
+                        "logits.npy: the last timed step's logits) to DIR; "
+                        "at most 64 MB per rank, ranks above 0 write "
+                        "<name>.rank<r>.npy")
     args = p.parse_args()
 
     if args.stream:
@@ -68,8 +118,9 @@ def main() -> int:
     budget = spec.max_seq_len - args.warmup - args.steps - 16
     if args.prompt_len > max(budget, 16):
         args.prompt_len = max(budget, 16)
-    # floor of 2048 on GPU so the post-timing agent tool-turn measurement
-    # (tool_turn_p50_s below) has context for real rendered prompts
+    # floor of 2048 on GPU so the --full agent tool-turn measurement
+    # (tool_turn_p50_s below) has context for real rendered prompts; plain
+    # runs keep it so both time the same engine shape
     max_seq = min(spec.max_seq_len,
                   max(args.prompt_len + args.warmup + args.steps + 64,
                       2048 if has_gpu else 0))
@@ -93,6 +144,9 @@ def main() -> int:
     rng = torch.Generator().manual_seed(99 if tp_mode else 99 + rank)
     prompt_ids = torch.randint(4, 260, (args.prompt_len,), generator=rng).tolist()
 
+    last = {}
+    if args.dump_outputs:
+        _record_logits(engine.model, last)
     engine.ensure_graph()               # capture outside the prefill timing
     tp0 = time.perf_counter()
     engine.prefill(prompt_ids)
@@ -135,14 +189,23 @@ def main() -> int:
     value = total_tokens / t_max
     ms_per_step = t_max / args.steps * 1000.0
 
-    # Second half of the BASELINE metric: p50 agent tool-turn latency,
-    # measured AFTER the timed region through the real Assistant stack
-    # (rank 0, single-agent configs only). Also gives the driver's SMI
-    # sampler several seconds of real GPU work to observe (r01's
-    # gpu_busy record was empty because the timed region was 77 ms).
+    # What a caller of the decode path receives: the token ids (prefill's
+    # first token, then one per warmup/timed step) and, for the last timed
+    # step, the logits they were sampled from. Written before anything
+    # else touches the engine state.
+    if args.dump_outputs:
+        n_tok = min(1 + args.warmup + args.steps, engine.out_tokens.shape[1])
+        arrays = {"tokens": engine.out_tokens[:, :n_tok].double().cpu().numpy()}
+        if "logits" in last:
+            arrays["logits"] = last["logits"].float().cpu().numpy()
+        _dump_outputs(args.dump_outputs, arrays, rank)
+
+    # --full — second half of the BASELINE metric: p50 agent tool-turn
+    # latency, measured AFTER the timed region through the real Assistant
+    # stack (rank 0, single-agent configs only).
     turn_stats = {}
-    if rank == 0 and not tp_mode and world <= 1 and args.batch == 1 \
-            and has_gpu:
+    if args.full and rank == 0 and not tp_mode and world <= 1 \
+            and args.batch == 1 and has_gpu:
         from fei_amd.core.turn_bench import measure_tool_turns
         turn_stats = measure_tool_turns(engine, n_turns=9, max_new=96)
 

@@ -20,11 +20,11 @@ run() {
 : > "$out"
 echo "# all_benches $(date -u +%Y-%m-%dT%H:%M:%SZ) $(hostname)" | tee -a "$out"
 
-run python bench.py --steps 256 --warmup 32                       # headline 8B
+run python bench.py --full --steps 256 --warmup 32                # headline 8B + tool-turn p50
 run python bench.py --steps 256 --warmup 32 --batch 8             # 8 sessions
-run python bench.py --steps 256 --warmup 32 --weights-fp8         # fp8 mode
-run python bench.py --model llama3-70b --prompt-len 256 --steps 48 --warmup 8
-run python bench.py --model llama3-1b --steps 256 --warmup 32
+run python bench.py --full --steps 256 --warmup 32 --weights-fp8  # fp8 mode
+run python bench.py --full --model llama3-70b --prompt-len 256 --steps 48 --warmup 8
+run python bench.py --full --model llama3-1b --steps 256 --warmup 32
 run python scripts/bench_spec.py llama3-8b 256
 run python scripts/bench_gemv.py
 run python scripts/bench_sessions.py

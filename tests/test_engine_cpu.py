@@ -16,7 +16,10 @@ from fei_amd.parallel.pg import ParallelContext
 
 @pytest.fixture(scope="module")
 def engine():
-    return LocalEngine.create("llama3-tiny", max_seq_len=128, seed=7)
+    # pinned to the CPU reference path: the from-scratch check below builds
+    # its independent model on CPU, and weights are seeded per device
+    return LocalEngine.create("llama3-tiny", max_seq_len=128, seed=7,
+                              device=torch.device("cpu"))
 
 
 def test_tokenizer_roundtrip():
@@ -567,7 +570,8 @@ def test_packaged_spm_tokenizer_default():
 def test_hbm_seq_plumbing_cpu():
     """max_seq_len='hbm' resolves to the spec window on CPU (the sizing
     toward 288 GB happens on GPU; tests/test_engine_gpu.py covers it)."""
-    eng = LocalEngine.create("llama3-tiny", max_seq_len="hbm", seed=7)
+    eng = LocalEngine.create("llama3-tiny", max_seq_len="hbm", seed=7,
+                             device=torch.device("cpu"))
     assert eng.max_seq_len == eng.spec.max_seq_len
     out = eng.generate("abc", max_new_tokens=4, stop_on_eos=False)
     assert len(out["token_ids"]) == 4

@@ -53,7 +53,8 @@ def test_two_rank_federation(tmp_path):
     env = dict(os.environ)
     env["FED_WORK"] = str(tmp_path)
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.setdefault("PYTHONPATH", os.getcwd())
+    env.setdefault("PYTHONPATH", os.path.dirname(
+        os.path.dirname(os.path.abspath(__file__))))
     proc = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

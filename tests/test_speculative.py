@@ -55,7 +55,9 @@ def test_ngram_matches_brute_force():
 
 @pytest.fixture(scope="module")
 def engine():
-    return LocalEngine.create("llama3-tiny")
+    # CPU reference path: exact-argmax agreement between the block-verify
+    # prefill and single-token decode is an fp32 invariant
+    return LocalEngine.create("llama3-tiny", device=torch.device("cpu"))
 
 
 def _ids(res):

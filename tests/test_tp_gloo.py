@@ -9,6 +9,8 @@ import sys
 import pytest
 import torch
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 WORKER = r"""
 import os, json, torch
 from fei_amd.engine.config import get_spec
@@ -61,7 +63,7 @@ def test_tp2_matches_tp1(tmp_path):
     env = dict(os.environ)
     env["TP_OUT"] = str(out_file)
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.setdefault("PYTHONPATH", os.getcwd())
+    env.setdefault("PYTHONPATH", ROOT)
     proc = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -91,7 +93,7 @@ from fei_amd.parallel.pg import init_from_env
 ctx = init_from_env(backend="gloo")
 model = os.environ.get("TP_MODEL", "llama3-tiny")
 eng = LocalEngine.create(model, max_seq_len=96, seed=11, tp=ctx,
-                         use_hip_graph=False)
+                         use_hip_graph=False, device=torch.device("cpu"))
 prompt = [1, 5, 9, 13, 21, 33, 7]
 out = eng.generate(prompt, max_new_tokens=10, stop_on_eos=False)
 if ctx.rank == 0:
@@ -108,7 +110,7 @@ def _run_tp_engine(tmp_path, nproc: int, model: str, port: int):
     env["TP_OUT"] = str(out_file)
     env["TP_MODEL"] = model
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.setdefault("PYTHONPATH", os.getcwd())
+    env.setdefault("PYTHONPATH", ROOT)
     for attempt in range(3):       # rendezvous ports can linger in TIME_WAIT
         proc = subprocess.run(
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
@@ -125,7 +127,8 @@ def _run_tp_engine(tmp_path, nproc: int, model: str, port: int):
 def _engine_reference(model: str):
     from fei_amd.engine.engine import LocalEngine
 
-    eng = LocalEngine.create(model, max_seq_len=96, seed=11)
+    eng = LocalEngine.create(model, max_seq_len=96, seed=11,
+                             device=torch.device("cpu"))
     return eng.generate([1, 5, 9, 13, 21, 33, 7], max_new_tokens=10,
                         stop_on_eos=False)["token_ids"]
 
@@ -213,7 +216,7 @@ from fei_amd.parallel.pg import init_from_env
 
 ctx = init_from_env(backend="gloo")
 eng = LocalEngine.create("llama3-tiny", max_seq_len=96, seed=11, tp=ctx,
-                         use_hip_graph=False)
+                         use_hip_graph=False, device=torch.device("cpu"))
 out = eng.generate([1, 5, 9, 13], max_new_tokens=8, temperature=0.8,
                    stop_on_eos=False)
 with open(os.environ["TP_OUT"] + f".rank{ctx.rank}", "w") as f:
@@ -232,7 +235,7 @@ def test_tp2_sampled_ranks_agree(tmp_path):
     env = dict(os.environ)
     env["TP_OUT"] = str(out_file)
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.setdefault("PYTHONPATH", os.getcwd())
+    env.setdefault("PYTHONPATH", ROOT)
     for attempt in range(3):
         proc = subprocess.run(
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
