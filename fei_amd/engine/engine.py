@@ -116,6 +116,10 @@ class LocalEngine:
         self._fused_norm_env = _os.environ.get("FEI_FUSED_NORM")
         self.seed = seed
         self.temperature = 0.0       # graph-captured; set before capture
+        # sampling filters (0 / 1.0 = off): graph-captured and, like
+        # temperature, persistent until the next generate*() call sets them
+        self.top_k = 0
+        self.top_p = 1.0
         if tokenizer is None:
             tok_path = _os.environ.get("FEI_TOKENIZER")
             if tok_path == "byte":
@@ -193,6 +197,9 @@ class LocalEngine:
                                       dtype=torch.int32, device=device)
         self.sample_ws = torch.zeros(self.B, SAMPLE_CHUNKS, 2,
                                      dtype=torch.float32, device=device)
+        # filtered sampler's per-row (threshold value, kept count) output
+        self.sample_info = torch.zeros(self.B, 2, dtype=torch.float32,
+                                       device=device)
         Hq_l, D = self.model.hq_l, self.model.D
         # sized from self.attn_splits (NOT the ctor arg: FEI_ATTN_SPLITS
         # overrides it, and an undersized workspace is an out-of-bounds
@@ -285,6 +292,43 @@ class LocalEngine:
 
     # -- decode step ---------------------------------------------------------
 
+    def _filter_active(self) -> bool:
+        return self.temperature > 0 and (self.top_k > 0 or self.top_p < 1.0)
+
+    def _set_sampling(self, temperature: float, top_k: int,
+                      top_p: float) -> None:
+        """Validate and install the sampling parameters of one request."""
+        if top_k < 0:
+            raise ValueError(f"top_k must be >= 0, got {top_k}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+        self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+        if self.tp.is_distributed and self._filter_active():
+            raise ValueError(
+                "top_k / top_p filtering is not supported under tensor "
+                "parallelism (the sampler sees only a vocab shard); use "
+                "top_k=0, top_p=1.0")
+
+    def _sample(self, logits: torch.Tensor) -> None:
+        """Sample self.token (and out_tokens[:, step]) from ``logits``:
+        the plain sampler, or the top-k / top-p kernel when a filter is
+        active. Used by every decode step and by the prefills, so the first
+        token is filtered like the rest."""
+        if self._filter_active():
+            ops.sample_filtered(logits, self.token, self.step,
+                                self.sample_info, out_tokens=self.out_tokens,
+                                temperature=self.temperature, seed=self.seed,
+                                top_k=self.top_k, top_p=self.top_p)
+        else:
+            ops.sample(logits, self.token, self.step,
+                       self.sample_ws.view(self.B, -1),
+                       out_tokens=self.out_tokens,
+                       temperature=self.temperature, seed=self.seed,
+                       nchunks=SAMPLE_CHUNKS)
+
+    def _sampling_params(self) -> tuple:
+        return (self.temperature, self.seed, self.top_k, self.top_p)
+
     def _decode_step(self) -> None:
         if self.tp.is_distributed:
             return self._decode_step_tp()
@@ -292,11 +336,7 @@ class LocalEngine:
             logits = self.model.forward_decode_stream(
                 self.token, self.pos, self.k_caches, self.v_caches,
                 self._stream_ws, self._stream_bufs)
-            ops.sample(logits, self.token, self.step,
-                       self.sample_ws.view(self.B, -1),
-                       out_tokens=self.out_tokens,
-                       temperature=self.temperature, seed=self.seed,
-                       nchunks=SAMPLE_CHUNKS)
+            self._sample(logits)
             ops.advance(self.pos, self.step, max_pos=self.max_seq_len - 1)
             return
         logits = self.model.forward_decode(
@@ -304,9 +344,7 @@ class LocalEngine:
             attn_splits=self.attn_splits, workspace=self.attn_ws,
             fused_attn=self.fused_attn, attn_out=self.attn_out,
             fused_norm=self.fused_norm)
-        ops.sample(logits, self.token, self.step, self.sample_ws.view(self.B, -1),
-                   out_tokens=self.out_tokens, temperature=self.temperature,
-                   seed=self.seed, nchunks=SAMPLE_CHUNKS)
+        self._sample(logits)
         ops.advance(self.pos, self.step, max_pos=self.max_seq_len - 1)
 
     def _decode_step_tp(self) -> None:
@@ -388,18 +426,21 @@ class LocalEngine:
             self.attn_ws[2].zero_()
         torch.cuda.synchronize()
         self._graph = g
-        self._graph_params = (self.temperature, self.seed)
+        self._graph_params = self._sampling_params()
         logger.info("decode step captured into hipGraph")
 
     def ensure_graph(self) -> None:
         if not self.use_graph:
             return
-        # temperature and seed are kernel ARGUMENTS baked into the capture:
-        # a later generate() with different sampling params must recapture
-        # or the graph would silently sample with the old ones
-        if self._graph is not None and \
-                getattr(self, "_graph_params", None) != (self.temperature,
-                                                         self.seed):
+        # temperature, seed and the top-k / top-p filter are kernel
+        # ARGUMENTS baked into the capture (the filter also selects WHICH
+        # sampler kernel is captured): a later generate() with different
+        # sampling params must recapture or the graph would silently sample
+        # with the old ones
+        have = getattr(self, "_graph_params", None)
+        if have is not None and len(have) == 2:
+            have = (*have, 0, 1.0)       # (temperature, seed): no filter
+        if self._graph is not None and have != self._sampling_params():
             logger.info("sampling params changed; recapturing decode graph")
             self._graph = None
         if self._graph is None:
@@ -471,10 +512,7 @@ class LocalEngine:
                                             self.v_caches)
         self.step.zero_()
         self.out_tokens.zero_()
-        ops.sample(logits.to(self.dtype), self.token, self.step,
-                   self.sample_ws.view(self.B, -1), out_tokens=self.out_tokens,
-                   temperature=self.temperature, seed=self.seed,
-                   nchunks=SAMPLE_CHUNKS)
+        self._sample(logits.to(self.dtype))
         self.pos.fill_(from_pos + S)
         if self.is_gpu:
             torch.cuda.synchronize(self.device)
@@ -606,16 +644,20 @@ class LocalEngine:
                  temperature: float = 0.0, stop_on_eos: bool = True,
                  from_pos: int = 0,
                  speculative: Optional[bool] = None,
-                 stop: Optional[List[str]] = None) -> Dict[str, object]:
+                 stop: Optional[List[str]] = None,
+                 top_k: int = 0, top_p: float = 1.0) -> Dict[str, object]:
         """Prefill + decode; returns text and timing metrics. ``from_pos``
         enables prefix caching: the prompt's first ``from_pos`` tokens are
         already in the KV caches and only the remainder is prefilled.
         ``speculative`` (default: FEI_SPEC_DECODE env) uses prompt-lookup
         speculative decoding — greedy/batch-1 only, token-identical output;
-        pays on contexts that repeat themselves (tool output, code)."""
+        pays on contexts that repeat themselves (tool output, code).
+        ``top_k`` / ``top_p`` (with temperature > 0) restrict sampling to the
+        tie-inclusive top-k / nucleus set of the raw logits, on the same
+        graph path as plain sampling."""
+        self._set_sampling(temperature, top_k, top_p)
         prompt_ids, new_ids, from_pos, max_new_tokens = self._prep_prompt(
             prompt, max_new_tokens, from_pos)
-        self.temperature = temperature
         if self.is_gpu:
             torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
@@ -694,16 +736,17 @@ class LocalEngine:
                         max_new_tokens: int = 256,
                         temperature: float = 0.0, stop_on_eos: bool = True,
                         from_pos: int = 0, chunk: int = 16,
-                        stop: Optional[List[str]] = None):
+                        stop: Optional[List[str]] = None,
+                        top_k: int = 0, top_p: float = 1.0):
         """Streaming generate (batch 1): yields a dict per decoded chunk —
         {"new_token_ids", "text", "done"} where ``text`` is the cumulative
         decode (byte tokens can split multi-byte characters, so deltas are
         only stable on the cumulative string). The final chunk carries the
         full metrics of generate()."""
         assert self.B == 1, "streaming is a batch-1 interactive path"
+        self._set_sampling(temperature, top_k, top_p)
         prompt_ids, new_ids, from_pos, max_new_tokens = self._prep_prompt(
             prompt, max_new_tokens, from_pos)
-        self.temperature = temperature
         if self.is_gpu:
             torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
@@ -872,10 +915,7 @@ class LocalEngine:
         logits = all_logits[torch.arange(self.B, device=self.device), idx]
         self.step.zero_()
         self.out_tokens.zero_()
-        ops.sample(logits.to(self.dtype).contiguous(), self.token, self.step,
-                   self.sample_ws.view(self.B, -1), out_tokens=self.out_tokens,
-                   temperature=self.temperature, seed=self.seed,
-                   nchunks=SAMPLE_CHUNKS)
+        self._sample(logits.to(self.dtype).contiguous())
         self.pos.copy_(torch.tensor(lens, dtype=torch.int32,
                                     device=self.device))
         if self.is_gpu:
@@ -885,14 +925,15 @@ class LocalEngine:
             self.step += 1
 
     def generate_batch(self, prompts, max_new_tokens: int = 256,
-                       temperature: float = 0.0, stop_on_eos: bool = True):
+                       temperature: float = 0.0, stop_on_eos: bool = True,
+                       top_k: int = 0, top_p: float = 1.0):
         """Independent agent sessions in one batch: B different prompts ->
         B completions, decoded together (per-row positions/EOS)."""
         ids = [self.tokenizer.encode(p) if isinstance(p, str) else list(p)
                for p in prompts]
         budget = self.max_seq_len - max(len(p) for p in ids) - 1
         max_new_tokens = max(1, min(max_new_tokens, budget))
-        self.temperature = temperature
+        self._set_sampling(temperature, top_k, top_p)
         self.prefill_ragged(ids)
         rows = self.decode(max_new_tokens, stop_on_eos=stop_on_eos)
         return [{"text": self.tokenizer.decode(r), "token_ids": r}

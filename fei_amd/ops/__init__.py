@@ -64,6 +64,8 @@ def _try_load() -> None:
     lib.fei_sample_onepass.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _f, _u64,
                                        _i, _vp]
     lib.fei_sample_shard.argtypes = [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _vp]
+    lib.fei_sample_filtered.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                        _f, _f, _u64, _i, _vp]
     lib.fei_stream_layer_check.argtypes = [_i, _i, _i, _i, _i]
     lib.fei_stream_layer_check.restype = _i
     lib.fei_stream_layer.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -381,6 +383,43 @@ def sample(logits: torch.Tensor, token: torch.Tensor,
         lib.fei_sample(_ptr(logits), _ptr(token), out_ptr, _ptr(step),
                        _ptr(workspace), B, V, nchunks, temperature, seed,
                        max_new, _stream())
+    return token
+
+
+def sample_filtered(logits: torch.Tensor, token: torch.Tensor,
+                    step: torch.Tensor, info: torch.Tensor,
+                    out_tokens: Optional[torch.Tensor] = None,
+                    temperature: float = 0.0, seed: int = 0,
+                    top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+    """sample() restricted to the top-k / top-p keep set of each row
+    (reference.filter_keep: tie-inclusive, top-k then top-p on the raw
+    logits, temperature only at the draw). One kernel for any B; all state
+    on device and the filter parameters are kernel arguments, so the call is
+    hipGraph-capturable. ``info`` [B,2] f32 receives (smallest kept value,
+    kept count as int32 bits). With the filter inactive (top_k 0 or >= V and
+    top_p >= 1) the token equals sample()'s; temperature <= 0 is greedy."""
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0, got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    B, V = logits.shape
+    if not logits.is_cuda:
+        keep, thr, count = ref.filter_keep(logits, top_k, top_p)
+        info[:, 0] = thr
+        info[:, 1].view(torch.int32).copy_(count)
+        if keep.all():
+            masked = logits
+        else:
+            masked = logits.float().masked_fill(~keep, float("-inf"))
+        # the (seed, step)-seeded draw of sample()'s CPU path
+        return sample(masked, token, step, None, out_tokens=out_tokens,
+                      temperature=temperature, seed=seed)
+    lib = require_lib()
+    max_new = out_tokens.shape[1] if out_tokens is not None else 0
+    out_ptr = _ptr(out_tokens) if out_tokens is not None else None
+    lib.fei_sample_filtered(_ptr(logits), _ptr(token), out_ptr, _ptr(step),
+                            _ptr(info), B, V, int(top_k), float(top_p),
+                            float(temperature), int(seed), max_new, _stream())
     return token
 
 

@@ -233,6 +233,42 @@ def topp_mask(logits: torch.Tensor, p: float) -> torch.Tensor:
     return out.to(logits.dtype)
 
 
+def filter_keep(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Tie-inclusive top-k / top-p keep set, computed in fp64 on the exact
+    input values (so it does not depend on any sort order).
+
+    Order as in the eager path: top-k first, then top-p, both on the RAW
+    logits (temperature applies only at the draw).
+      top-k (0 < k < V): tau_k = k-th largest value counting multiplicity,
+        K = {i : x_i >= tau_k}; otherwise K is everything.
+      top-p (p < 1): q_i = exp(x_i - max) / sum_K; a value group v of K is
+        kept iff above(v) = sum_{i in K, x_i > v} q_i < p (the max group is
+        therefore always kept).
+    Equals topk_mask -> topp_mask except inside the boundary tie group,
+    which is kept whole here.
+
+    Returns (keep [B,V] bool, thr [B] f32 = smallest kept value,
+    count [B] i32 = number of kept tokens), on the CPU."""
+    x = logits.detach().to("cpu").to(torch.float64)
+    B, V = x.shape
+    if 0 < top_k < V:
+        tau = torch.topk(x, top_k, dim=-1).values[:, -1:]
+        keep = x >= tau
+    else:
+        keep = torch.ones(B, V, dtype=torch.bool)
+    if top_p < 1.0:
+        for b in range(B):
+            vals, counts = torch.unique(x[b][keep[b]], return_counts=True)
+            vals, counts = vals.flip(0), counts.flip(0)      # descending
+            w = torch.exp(vals - vals[0]) * counts.to(torch.float64)
+            above = (w.cumsum(0) - w) / w.sum()
+            kept_vals = vals[above < top_p]
+            keep[b] &= x[b] >= kept_vals[-1]
+    thr = torch.where(keep, x, torch.full_like(x, float("inf"))).amin(dim=-1)
+    return keep, thr.to(torch.float32), keep.sum(dim=-1).to(torch.int32)
+
+
 # -- fp8 weight quantization (OCP e4m3fn; decode-path serving mode) ----------
 
 def quant_fp8(w: torch.Tensor):

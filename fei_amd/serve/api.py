@@ -89,30 +89,30 @@ def create_app(engine: Optional[LocalEngine] = None,
                             # re-prefill only the delta
 
     def _generate(prompt: str, req) -> dict:
+        # top_k / top_p requests take the same path as every other request
+        # (the filter runs in the sampler kernel), so the prefix cache, stop
+        # strings and stop_on_eos apply to them too
         with lock:
-            if req.temperature > 0 and (req.top_k or req.top_p < 1.0):
-                out = eng.generate_sampled(
-                    prompt, max_new_tokens=req.max_tokens,
-                    temperature=req.temperature, top_k=req.top_k,
-                    top_p=req.top_p)
-                cache["ids"] = []
-            else:
-                ids = eng.tokenizer.encode(prompt)
-                n = 0
-                if getattr(req, "cache_prefix", True) and eng.B == 1:
-                    limit = min(len(cache["ids"]), len(ids) - 1)
-                    while n < limit and ids[n] == cache["ids"][n]:
-                        n += 1
+            ids = eng.tokenizer.encode(prompt)
+            n = 0
+            if getattr(req, "cache_prefix", True) and eng.B == 1:
+                limit = min(len(cache["ids"]), len(ids) - 1)
+                while n < limit and ids[n] == cache["ids"][n]:
+                    n += 1
+            try:
                 out = eng.generate(
                     ids, max_new_tokens=req.max_tokens,
                     temperature=req.temperature,
                     stop_on_eos=getattr(req, "stop_on_eos", True),
                     speculative=getattr(req, "speculative", None),
                     stop=getattr(req, "stop", None),
-                    from_pos=n)
-                # drop the final generated token: only sampled, its KV row
-                # is never written (same rule as the agent backend)
-                cache["ids"] = ids + list(out["token_ids"])[:-1]
+                    from_pos=n, top_k=req.top_k, top_p=req.top_p)
+            except ValueError as e:          # bad top_k / top_p
+                from fastapi import HTTPException
+                raise HTTPException(status_code=422, detail=str(e))
+            # drop the final generated token: only sampled, its KV row
+            # is never written (same rule as the agent backend)
+            cache["ids"] = ids + list(out["token_ids"])[:-1]
         return out
 
     @app.get("/health")
@@ -170,7 +170,8 @@ def create_app(engine: Optional[LocalEngine] = None,
                             req.prompt, max_new_tokens=req.max_tokens,
                             temperature=req.temperature,
                             stop_on_eos=req.stop_on_eos,
-                            stop=req.stop):
+                            stop=req.stop, top_k=req.top_k,
+                            top_p=req.top_p):
                         delta = c["text"][len(prev):]
                         prev = c["text"]
                         payload = {"object": "text_completion.chunk",
@@ -225,7 +226,8 @@ def create_app(engine: Optional[LocalEngine] = None,
                     prev = ""
                     for c in eng.generate_stream(
                             prompt, max_new_tokens=req.max_tokens,
-                            temperature=req.temperature):
+                            temperature=req.temperature, top_k=req.top_k,
+                            top_p=req.top_p):
                         delta = c["text"][len(prev):]
                         prev = c["text"]
                         payload = {"object": "chat.completion.chunk",
