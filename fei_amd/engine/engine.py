@@ -54,6 +54,7 @@ class LocalEngine:
         weight_quant: Optional[str] = None,    # None | "fp8" (decode path)
         tokenizer=None,                        # default ByteTokenizer; or
                                                # SpmTokenizer(model_path)
+        kv_quant: Optional[str] = None,        # None | "fp8" (KV cache)
     ):
         self.spec = spec
         if device is None:
@@ -114,6 +115,26 @@ class LocalEngine:
         # ~3-5 TB/s vs 6.6 plain. The fused chain stays for fp8 decode
         # (its kernels are norm-fused) and via FEI_FUSED_NORM=1.
         self._fused_norm_env = _os.environ.get("FEI_FUSED_NORM")
+        # fp8 (e4m3fn + per-row f32 scale) KV cache: halves KV bytes and KV
+        # memory; opt-in (kv_quant="fp8" / FEI_KV_QUANT=fp8). Prefill, the
+        # split-K decode attention and the append run csrc/kv_fp8.hip.
+        self.kv_quant = kv_quant or _os.environ.get("FEI_KV_QUANT") or None
+        if self.kv_quant not in (None, "fp8"):
+            raise ValueError(
+                f"kv_quant must be None or 'fp8', got {self.kv_quant!r}")
+        if self.kv_quant == "fp8":
+            if self.fused_attn:
+                raise ValueError(
+                    "kv_quant='fp8' conflicts with FEI_FUSED_ATTN=1: the "
+                    "fused single-pass attention kernel has no fp8 KV form")
+            if _os.environ.get("FEI_STREAM_DECODE", "0") == "1":
+                raise ValueError(
+                    "kv_quant='fp8' conflicts with FEI_STREAM_DECODE=1: the "
+                    "persistent stream engine reads a bf16 KV cache")
+            if self.tp.is_distributed:
+                raise ValueError(
+                    "kv_quant='fp8' conflicts with tensor parallelism "
+                    "(not verified on more than one GPU)")
         self.seed = seed
         self.temperature = 0.0       # graph-captured; set before capture
         # sampling filters (0 / 1.0 = off): graph-captured and, like
@@ -174,7 +195,8 @@ class LocalEngine:
                         self.max_seq_len,
                         self._kv_bytes_per_token() * self.B *
                         self.max_seq_len / 2 ** 30)
-        self.k_caches, self.v_caches = self.model.new_kv_cache(self.B, self.max_seq_len)
+        self.k_caches, self.v_caches = self.model.new_kv_cache(
+            self.B, self.max_seq_len, kv_quant=self.kv_quant)
         logger.info("model %s init in %.1fs (%.2f GB params)", spec.name,
                     time.perf_counter() - t0, self.model.param_bytes() / 2**30)
         self.weight_quant = weight_quant or _os.environ.get("FEI_WEIGHT_QUANT")
@@ -266,10 +288,20 @@ class LocalEngine:
     def _kv_bytes_per_token(self) -> int:
         s = self.spec
         el = 2 if self.dtype == torch.bfloat16 else 4
+        # bytes of one cached head-row: D elements, or D codes + one f32
+        # scale in the fp8 format
+        row = s.head_dim + 4 if self.kv_quant == "fp8" else s.head_dim * el
         return (s.num_layers * (s.num_kv_heads //
                                 (self.tp.world_size
                                  if self.tp.is_distributed else 1))
-                * s.head_dim * 2 * el)
+                * 2 * row)
+
+    @property
+    def kv_dtype(self) -> str:
+        """Element format of the KV cache: "fp8", "bf16" or "fp32"."""
+        if self.kv_quant == "fp8":
+            return "fp8"
+        return "bf16" if self.dtype == torch.bfloat16 else "fp32"
 
     def _resolve_hbm_seq(self) -> int:
         """Largest KV window that fits the remaining device memory with
@@ -394,8 +426,12 @@ class LocalEngine:
         }
         # warmup at positions 1..2: snapshot those KV rows in every layer
         kv_rows = slice(1, 4)
-        saved_k = [k[:, :, kv_rows].clone() for k in self.k_caches]
-        saved_v = [v[:, :, kv_rows].clone() for v in self.v_caches]
+        # (an fp8 cache is two tensors per layer: codes AND row scales)
+        kv_tensors = []
+        for c in (*self.k_caches, *self.v_caches):
+            kv_tensors += ([c.data, c.scale] if isinstance(c, ops.QuantKV)
+                           else [c])
+        saved_kv = [t[:, :, kv_rows].clone() for t in kv_tensors]
         # state must be valid during warmup/capture: pretend one token exists
         self.pos.fill_(1)
         self.step.zero_()
@@ -414,10 +450,8 @@ class LocalEngine:
         self.pos.copy_(saved["pos"])
         self.step.copy_(saved["step"])
         self.out_tokens[:, :4].copy_(saved["out"])
-        for k, sk in zip(self.k_caches, saved_k):
-            k[:, :, kv_rows].copy_(sk)
-        for v, sv in zip(self.v_caches, saved_v):
-            v[:, :, kv_rows].copy_(sv)
+        for t, st in zip(kv_tensors, saved_kv):
+            t[:, :, kv_rows].copy_(st)
         # fused-combine done-flags are (pos, layer)-tagged: the warmup ran
         # at pos 1..2, and the first real replay may run at those same
         # positions — stale matching tags would let the in-kernel reducer
@@ -686,6 +720,7 @@ class LocalEngine:
             "new_tokens": new_tokens,
             "prefill_s": t1 - t0,
             "decode_s": decode_s,
+            "kv_dtype": self.kv_dtype,
             "prefill_tok_s": len(new_ids) / max(t1 - t0, 1e-9),
             "decode_tok_s": (max(new_tokens - 1, 0) * self.B) / max(decode_s, 1e-9),
         }
@@ -794,6 +829,7 @@ class LocalEngine:
                     "new_tokens": len(row),
                     "prefill_s": t1 - t0,
                     "decode_s": decode_s,
+                    "kv_dtype": self.kv_dtype,
                     "prefill_tok_s": len(new_ids) / max(t1 - t0, 1e-9),
                     "decode_tok_s": max(len(row) - 1, 0) / max(decode_s, 1e-9),
                 }

@@ -154,9 +154,21 @@ class LlamaModel:
 
     # -- kv cache ------------------------------------------------------------
 
-    def new_kv_cache(self, batch: int, max_seq: Optional[int] = None):
+    def new_kv_cache(self, batch: int, max_seq: Optional[int] = None,
+                     kv_quant: Optional[str] = None):
+        """Per-layer K and V cache lists. ``kv_quant="fp8"``: ops.QuantKV
+        entries (e4m3fn codes + one f32 scale per row) instead of tensors."""
         max_seq = max_seq or self.max_seq_len
         shape = (batch, self.hkv_l, max_seq, self.D)
+        if kv_quant == "fp8":
+            return (
+                [ops.QuantKV.zeros(shape, self.device)
+                 for _ in range(self.spec.num_layers)],
+                [ops.QuantKV.zeros(shape, self.device)
+                 for _ in range(self.spec.num_layers)],
+            )
+        if kv_quant is not None:
+            raise ValueError(f"unknown kv_quant {kv_quant!r}")
         return (
             [torch.zeros(shape, device=self.device, dtype=self.dtype)
              for _ in range(self.spec.num_layers)],

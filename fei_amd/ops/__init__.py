@@ -66,6 +66,19 @@ def _try_load() -> None:
     lib.fei_sample_shard.argtypes = [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _vp]
     lib.fei_sample_filtered.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                         _f, _f, _u64, _i, _vp]
+    lib.fei_rope_kv8_decode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _i, _i, _i, _i, _i, _l, _l,
+                                        _vp]
+    lib.fei_rope_kv8_prefill.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _i, _i, _i, _i, _i, _i,
+                                         _l, _l, _vp]
+    lib.fei_attn_decode_kv8.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _i, _i, _i, _i, _i, _i, _f, _l,
+                                        _vp, _vp, _vp, _l, _vp]
+    lib.fei_attn_decode_kv8.restype = _i
+    lib.fei_attn_prefill_kv8.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _i, _i, _i, _i, _i, _i, _f, _l, _vp]
+    lib.fei_attn_prefill_kv8.restype = _i
     lib.fei_stream_layer_check.argtypes = [_i, _i, _i, _i, _i]
     lib.fei_stream_layer_check.restype = _i
     lib.fei_stream_layer.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -121,6 +134,50 @@ def _ptr(t: torch.Tensor) -> int:
 # ---------------------------------------------------------------------------
 
 
+class QuantKV:
+    """One layer's K (or V) cache in the fp8 storage format of
+    reference.quant_kv_fp8: ``data`` uint8 [B, Hkv, max_seq, D] e4m3fn codes
+    plus ``scale`` f32 [B, Hkv, max_seq], one per cached row. It takes a
+    tensor's place in the engine's k_caches / v_caches lists; the append and
+    attention entry points below dispatch on it."""
+
+    __slots__ = ("data", "scale")
+
+    def __init__(self, data: torch.Tensor, scale: torch.Tensor):
+        assert data.dtype == torch.uint8 and scale.dtype == torch.float32
+        assert tuple(scale.shape) == tuple(data.shape[:-1])
+        # the kernels take raw pointers and index rows as
+        # ((b*Hkv + h)*max_seq + p): a sliced or strided view would read
+        # the wrong rows; their 16 B / 8 B vector loads need an aligned base
+        assert data.is_contiguous() and scale.is_contiguous(), \
+            "QuantKV needs contiguous data and scale"
+        assert data.data_ptr() % 16 == 0, "QuantKV data must be 16 B aligned"
+        self.data = data
+        self.scale = scale
+
+    @classmethod
+    def zeros(cls, shape, device) -> "QuantKV":
+        return cls(torch.zeros(shape, dtype=torch.uint8, device=device),
+                   torch.ones(shape[:-1], dtype=torch.float32, device=device))
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    def dequant(self, length: Optional[int] = None) -> torch.Tensor:
+        """f32 [B, Hkv, length or max_seq, D] (reference / diagnostics)."""
+        n = self.data.shape[2] if length is None else length
+        return ref.dequant_kv_fp8(self.data[:, :, :n], self.scale[:, :, :n])
+
+
+def _kv8_pair(k_cache, v_cache) -> bool:
+    k8, v8 = isinstance(k_cache, QuantKV), isinstance(v_cache, QuantKV)
+    if k8 != v8:
+        raise TypeError("k_cache and v_cache must both be QuantKV or both "
+                        "be tensors")
+    return k8
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """RMSNorm over the last dim. x: [..., C] bf16 (GPU) / any float (CPU)."""
@@ -157,9 +214,16 @@ def fused_add_rmsnorm(x: torch.Tensor, residual: torch.Tensor,
 
 def rope_kv_decode(q, k, v, k_cache, v_cache, pos, table) -> torch.Tensor:
     """In-place RoPE on q; k roped + v appended into caches at pos[b].
-    q [B,Hq,D], k/v [B,Hkv,D], caches [B,Hkv,max_seq,D], pos [B] int32."""
+    q [B,Hq,D], k/v [B,Hkv,D], caches [B,Hkv,max_seq,D], pos [B] int32.
+    QuantKV caches: the rows are quantised on the way in (kv_fp8.hip)."""
+    kv8 = _kv8_pair(k_cache, v_cache)
     if not q.is_cuda:
-        q_out = ref.rope_kv_decode(q, k, v, k_cache, v_cache, pos, table)
+        if kv8:
+            q_out = ref.rope_kv_decode_fp8(
+                q, k, v, k_cache.data, k_cache.scale, v_cache.data,
+                v_cache.scale, pos, table)
+        else:
+            q_out = ref.rope_kv_decode(q, k, v, k_cache, v_cache, pos, table)
         q.copy_(q_out)
         return q
     lib = require_lib()
@@ -168,6 +232,14 @@ def rope_kv_decode(q, k, v, k_cache, v_cache, pos, table) -> torch.Tensor:
     assert q.stride(2) == 1 and q.stride(1) == D, "head rows must be contiguous"
     assert k.stride(1) == D and v.stride(1) == D
     assert k.stride(0) == v.stride(0)
+    if kv8:
+        assert D in (64, 128), f"fp8 KV append supports D in (64,128), got {D}"
+        lib.fei_rope_kv8_decode(_ptr(q), _ptr(k), _ptr(v), _ptr(k_cache.data),
+                                _ptr(k_cache.scale), _ptr(v_cache.data),
+                                _ptr(v_cache.scale), _ptr(table), _ptr(pos),
+                                B, Hq, Hkv, D, k_cache.shape[2],
+                                q.stride(0), k.stride(0), _stream())
+        return q
     lib.fei_rope_kv_decode(_ptr(q), _ptr(k), _ptr(v), _ptr(k_cache),
                            _ptr(v_cache), _ptr(table), _ptr(pos),
                            B, Hq, Hkv, D, k_cache.shape[2],
@@ -176,9 +248,16 @@ def rope_kv_decode(q, k, v, k_cache, v_cache, pos, table) -> torch.Tensor:
 
 
 def rope_kv_prefill(q, k, v, k_cache, v_cache, pos0, table) -> torch.Tensor:
-    """In-place RoPE on q [B,S,Hq,D]; k roped + v appended at pos0[b]+s."""
+    """In-place RoPE on q [B,S,Hq,D]; k roped + v appended at pos0[b]+s
+    (quantised per row when the caches are QuantKV)."""
+    kv8 = _kv8_pair(k_cache, v_cache)
     if not q.is_cuda:
-        q_out = ref.rope_kv_prefill(q, k, v, k_cache, v_cache, pos0, table)
+        if kv8:
+            q_out = ref.rope_kv_prefill_fp8(
+                q, k, v, k_cache.data, k_cache.scale, v_cache.data,
+                v_cache.scale, pos0, table)
+        else:
+            q_out = ref.rope_kv_prefill(q, k, v, k_cache, v_cache, pos0, table)
         q.copy_(q_out)
         return q
     lib = require_lib()
@@ -188,6 +267,14 @@ def rope_kv_prefill(q, k, v, k_cache, v_cache, pos0, table) -> torch.Tensor:
     assert q.stride(0) == S * q.stride(1), "token rows must be uniform"
     assert k.stride(2) == D and k.stride(0) == S * k.stride(1)
     assert k.stride(1) == v.stride(1)
+    if kv8:
+        assert D in (64, 128), f"fp8 KV append supports D in (64,128), got {D}"
+        lib.fei_rope_kv8_prefill(_ptr(q), _ptr(k), _ptr(v), _ptr(k_cache.data),
+                                 _ptr(k_cache.scale), _ptr(v_cache.data),
+                                 _ptr(v_cache.scale), _ptr(table), _ptr(pos0),
+                                 B, S, Hq, Hkv, D, k_cache.shape[2],
+                                 q.stride(1), k.stride(1), _stream())
+        return q
     lib.fei_rope_kv_prefill(_ptr(q), _ptr(k), _ptr(v), _ptr(k_cache),
                             _ptr(v_cache), _ptr(table), _ptr(pos0),
                             B, S, Hq, Hkv, D, k_cache.shape[2],
@@ -206,15 +293,25 @@ def attn_decode(q, k_cache, v_cache, pos, splits: int = 32,
     """Single-token GQA attention over n = pos[b]+1 cache entries.
     q [B,Hq,D] -> out [B,Hq,D]. The length is read on DEVICE (hipGraph).
     When (k, v, table) are given, the kernel also fuses the step's RoPE +
-    KV-append: q is the RAW qkv view and cache[pos] is written in-kernel."""
+    KV-append: q is the RAW qkv view and cache[pos] is written in-kernel.
+    QuantKV caches run the fp8 kernel (kv_fp8.hip): same partials, always
+    the separate combine launch."""
     B, Hq, D = q.shape
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    kv8 = _kv8_pair(k_cache, v_cache)
     if not q.is_cuda:
         if table is not None:
             rope_kv_decode(q, k, v, k_cache, v_cache, pos, table)
         seqlen = pos + 1
+        if kv8:
+            n = int(seqlen.max())
+            return ref.attn_decode(q, k_cache.dequant(n), v_cache.dequant(n),
+                                   seqlen, scale)
         return ref.attn_decode(q, k_cache, v_cache, seqlen, scale)
     lib = require_lib()
+    if kv8:
+        return _attn_decode_kv8(lib, q, k_cache, v_cache, pos, splits, scale,
+                                workspace, out, k, v, table)
     arrive = None
     if workspace is None:
         part_o = torch.empty(B, Hq, splits, D, dtype=torch.float32, device=q.device)
@@ -263,6 +360,47 @@ def attn_decode(q, k_cache, v_cache, pos, splits: int = 32,
     return out
 
 
+def _attn_decode_kv8(lib, q, k_cache, v_cache, pos, splits, scale, workspace,
+                     out, k, v, table) -> torch.Tensor:
+    B, Hq, D = q.shape
+    Hkv = k_cache.shape[1]
+    if workspace is None:
+        part_o = torch.empty(B, Hq, splits, D, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(B, Hq, splits, 2, dtype=torch.float32, device=q.device)
+    else:
+        # a 3rd element (fused-combine flags) is ignored: the fp8 path
+        # always takes the separate combine launch
+        part_o, part_ml = workspace[0], workspace[1]
+        assert part_o.shape[2] == splits and part_ml.shape[2] == splits, \
+            f"workspace sized for {part_o.shape[2]} splits, kernel asked {splits}"
+    if out is None:
+        out = torch.empty_like(q)
+    assert q.stride(2) == 1 and q.stride(1) == D
+    assert D in (64, 128), f"decode attention supports D in (64,128), got {D}"
+    # the combine kernel stages its 2*splits m/l values with D threads
+    assert 2 * splits <= D, \
+        f"fp8 decode attention needs 2*splits <= D (splits={splits}, D={D})"
+    assert Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8), \
+        f"unsupported GQA group size {Hq}/{Hkv}"
+    if table is not None:
+        assert k is not None and v is not None
+        assert k.stride(1) == D and k.stride(0) == v.stride(0)
+        kin, vin, cs, kv_bs = _ptr(k), _ptr(v), _ptr(table), k.stride(0)
+    else:
+        kin = vin = cs = None
+        kv_bs = 0
+    rc = lib.fei_attn_decode_kv8(
+        _ptr(q), _ptr(k_cache.data), _ptr(k_cache.scale), _ptr(v_cache.data),
+        _ptr(v_cache.scale), _ptr(part_o), _ptr(part_ml), _ptr(pos),
+        B, Hq, Hkv, D, k_cache.shape[2], splits, scale, q.stride(0),
+        kin, vin, cs, kv_bs, _stream())
+    if rc != 0:
+        raise RuntimeError(f"fei_attn_decode_kv8 refused the launch (rc={rc})")
+    lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
+                                B, Hq, D, splits, _stream())
+    return out
+
+
 def attn_decode_fused(q, k, v, k_cache, v_cache, pos, table,
                       scale: Optional[float] = None,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -272,6 +410,9 @@ def attn_decode_fused(q, k, v, k_cache, v_cache, pos, table,
     B, Hq, D = q.shape
     Hkv = k.shape[1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _kv8_pair(k_cache, v_cache):
+        raise ValueError("attn_decode_fused has no fp8 KV form; use "
+                         "attn_decode (split-K) with QuantKV caches")
     if not q.is_cuda:
         rope_kv_decode(q, k, v, k_cache, v_cache, pos, table)
         return ref.attn_decode(q, k_cache, v_cache, pos + 1, scale)
@@ -294,7 +435,14 @@ def attn_prefill(q, k_cache, v_cache, pos0, scale: Optional[float] = None,
     caches. q token s attends [0, pos0[b]+s] when causal, else [0, kv_len[b])."""
     B, S, Hq, D = q.shape
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    kv8 = _kv8_pair(k_cache, v_cache)
+    if kv8 and not causal:
+        raise ValueError("fp8 KV prefill attention is causal-only")
     if not q.is_cuda:
+        if kv8:
+            n = int(pos0.max()) + S
+            return ref.attn_prefill(q, k_cache.dequant(n), v_cache.dequant(n),
+                                    pos0, scale)
         if causal:
             return ref.attn_prefill(q, k_cache, v_cache, pos0, scale)
         # bidirectional reference: softmax over [0, kv_len)
@@ -302,6 +450,19 @@ def attn_prefill(q, k_cache, v_cache, pos0, scale: Optional[float] = None,
     lib = require_lib()
     if out is None:
         out = torch.empty_like(q)
+    if kv8:
+        assert q.stride(3) == 1 and q.stride(2) == D
+        assert q.stride(0) == S * q.stride(1)
+        assert out.is_contiguous()
+        rc = lib.fei_attn_prefill_kv8(
+            _ptr(q), _ptr(k_cache.data), _ptr(k_cache.scale),
+            _ptr(v_cache.data), _ptr(v_cache.scale), _ptr(out), _ptr(pos0),
+            B, S, Hq, k_cache.shape[1], D, k_cache.shape[2], scale,
+            q.stride(1), _stream())
+        if rc != 0:
+            raise RuntimeError(
+                f"fp8 KV prefill attention supports D in (64,128), got {D}")
+        return out
     if kv_len is None:
         kv_len = pos0  # unused when causal
     Hkv = k_cache.shape[1]

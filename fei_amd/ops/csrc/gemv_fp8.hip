@@ -227,30 +227,7 @@ k_gemv_swiglu_norm_fp8(u16* __restrict__ out, const u16* __restrict__ res,
 }
 
 // quantize bf16 rows -> e4m3fn + per-row scale (absmax/448), RNE on the
-// mantissa via float rounding: encode(w / scale).
-__device__ __forceinline__ unsigned char e4m3_encode(float f) {
-  if (f != f) return 0x7F;                  // NaN
-  const unsigned int bits = __float_as_uint(f);
-  const unsigned int s = bits >> 31;
-  float a = fabsf(f);
-  if (a > 448.f) a = 448.f;                 // saturate (no inf in e4m3fn)
-  // round to the e4m3 grid: scale into [1,2), round mantissa to 3 bits
-  if (a < 0.001953125f * 0.5f) return (unsigned char)(s << 7);  // -> 0
-  int e;
-  float mant = frexpf(a, &e);               // a = mant * 2^e, mant in [0.5,1)
-  mant *= 2.f; e -= 1;                      // mant in [1,2)
-  if (e < -6) {                             // subnormal: units of 2^-9
-    const int mi = (int)rintf(a * 512.f);   // a / 2^-9, RNE
-    if (mi > 7)                             // rounds up to the min normal
-      return (unsigned char)((s << 7) | (1 << 3));
-    return (unsigned char)((s << 7) | mi);
-  }
-  int mi = (int)rintf((mant - 1.f) * 8.f);  // 3-bit mantissa, RNE via rintf
-  if (mi == 8) { mi = 0; e += 1; }
-  if (e > 8) { e = 8; mi = 6; }             // clamp to 448 = 1.75*2^8
-  return (unsigned char)((s << 7) | ((e + 7) << 3) | mi);
-}
-
+// mantissa via float rounding: e4m3_encode(w / scale) (fei_common.h).
 __global__ void __launch_bounds__(256)
 k_quant_fp8_rows(unsigned char* __restrict__ w8, float* __restrict__ wscale,
                  const u16* __restrict__ w, int N, int K) {

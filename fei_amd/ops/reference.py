@@ -285,6 +285,69 @@ def dequant_fp8(w8: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     return w8.view(torch.float8_e4m3fn).float() * scales.unsqueeze(-1).float()
 
 
+# -- fp8 KV cache (OCP e4m3fn, one f32 scale per cached row) -----------------
+#
+# THE definition of the storage format; csrc/kv_fp8.hip matches it bit for
+# bit. A cached row = the D elements of one (batch, kv-head, position):
+#   data  uint8   [B, Hkv, max_seq, D]   e4m3fn codes
+#   scale float32 [B, Hkv, max_seq]      amax/448, or 1 for an all-zero row
+#   code = e4m3fn(x / scale): IEEE f32 division, round-to-nearest-even,
+#   saturating at +-448 (|x / scale| <= 448 up to one rounding, so the cast
+#   never reaches the NaN codes 0x7F / 0xFF).
+# x is the value the unquantised cache would have stored (bf16 on the GPU
+# path: K after RoPE and bf16 rounding; fp32 on the CPU engine).
+
+def quant_kv_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., D] -> (codes uint8 [..., D], scales f32 [...]). quant_fp8 on
+    each row; differs from it only in the scale REPORTED for an all-zero
+    row (1 instead of quant_fp8's clamp floor — the codes are 0 either way)."""
+    D = x.shape[-1]
+    rows = x.reshape(-1, D)
+    codes, scales = quant_fp8(rows)
+    zero = rows.float().abs().amax(dim=-1) == 0
+    scales = torch.where(zero, torch.ones_like(scales), scales)
+    return codes.view(x.shape), scales.view(x.shape[:-1])
+
+
+def dequant_kv_fp8(data: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """(codes [..., D], scales [...]) -> f32 [..., D]."""
+    return data.view(torch.float8_e4m3fn).float() * scale.float().unsqueeze(-1)
+
+
+def rope_kv_decode_fp8(q, k, v, k_data, k_scale, v_data, v_scale, pos,
+                       table) -> torch.Tensor:
+    """rope_kv_decode into an fp8 cache: the roped k (rounded to k.dtype, as
+    the unquantised cache would store it) and v are quantised per row and
+    written at pos[b]. Returns roped q."""
+    q_out = apply_rope(q, pos, table)
+    kq, ks = quant_kv_fp8(apply_rope(k, pos, table))
+    vq, vs = quant_kv_fp8(v)
+    for b in range(q.shape[0]):
+        p = int(pos[b])
+        k_data[b, :, p, :] = kq[b]
+        k_scale[b, :, p] = ks[b]
+        v_data[b, :, p, :] = vq[b]
+        v_scale[b, :, p] = vs[b]
+    return q_out
+
+
+def rope_kv_prefill_fp8(q, k, v, k_data, k_scale, v_data, v_scale, pos0,
+                        table) -> torch.Tensor:
+    """rope_kv_prefill into an fp8 cache (rows pos0[b] .. pos0[b]+S-1)."""
+    B, S = q.shape[0], q.shape[1]
+    positions = pos0.view(B, 1).long() + torch.arange(S, device=q.device).view(1, S)
+    q_out = apply_rope(q, positions, table)
+    kq, ks = quant_kv_fp8(apply_rope(k, positions, table))   # [B,S,Hkv,D]
+    vq, vs = quant_kv_fp8(v)
+    for b in range(B):
+        p = int(pos0[b])
+        k_data[b, :, p:p + S, :] = kq[b].transpose(0, 1)
+        k_scale[b, :, p:p + S] = ks[b].transpose(0, 1)
+        v_data[b, :, p:p + S, :] = vq[b].transpose(0, 1)
+        v_scale[b, :, p:p + S] = vs[b].transpose(0, 1)
+    return q_out
+
+
 def hash_gumbel(B: int, v_local: int, v_offset: int, seed: int,
                 step: int) -> torch.Tensor:
     """CPU replica of the GPU sampler's per-element Gumbel noise
