@@ -178,6 +178,14 @@ def _kv8_pair(k_cache, v_cache) -> bool:
     return k8
 
 
+def _check_gqa(name: str, Hq: int, Hkv: int) -> None:
+    """The decode-attention kernels are instantiated for GQA group sizes
+    1/2/4/8 only; the C entry points launch nothing for any other."""
+    if Hkv <= 0 or Hq % Hkv != 0 or Hq // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"{name}: unsupported GQA group Hq={Hq}, Hkv={Hkv} "
+                         "(Hq/Hkv must be 1, 2, 4 or 8)")
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """RMSNorm over the last dim. x: [..., C] bf16 (GPU) / any float (CPU)."""
@@ -312,6 +320,7 @@ def attn_decode(q, k_cache, v_cache, pos, splits: int = 32,
     if kv8:
         return _attn_decode_kv8(lib, q, k_cache, v_cache, pos, splits, scale,
                                 workspace, out, k, v, table)
+    _check_gqa("attn_decode", Hq, k_cache.shape[1])
     arrive = None
     if workspace is None:
         part_o = torch.empty(B, Hq, splits, D, dtype=torch.float32, device=q.device)
@@ -417,6 +426,12 @@ def attn_decode_fused(q, k, v, k_cache, v_cache, pos, table,
         rope_kv_decode(q, k, v, k_cache, v_cache, pos, table)
         return ref.attn_decode(q, k_cache, v_cache, pos + 1, scale)
     lib = require_lib()
+    _check_gqa("attn_decode_fused", Hq, Hkv)
+    # the kernel's osh[8][DEC_DMAX/2][2] holds 256/(D/2) key groups: D < 64
+    # would index past it
+    if D not in (64, 128):
+        raise ValueError(
+            f"attn_decode_fused supports D in (64,128), got {D}")
     assert q.stride(2) == 1 and q.stride(1) == D
     assert k.stride(1) == D and k.stride(0) == v.stride(0)
     if out is None:
@@ -831,7 +846,11 @@ def gemv_swiglu_norm(res: torch.Tensor, wnorm: torch.Tensor,
     K = res.shape[-1]
     I = wgu.shape[0] // 2
     if not res.is_cuda or not _gemv_ok(M, K):
-        return swiglu(torch.nn.functional.linear(rmsnorm(res, wnorm, eps), wgu))
+        # normed activation rounds to res.dtype, g/u stay f32 through silu
+        # (the kernel's semantics)
+        gu = torch.nn.functional.linear(rmsnorm(res, wnorm, eps).float(),
+                                        wgu.float())
+        return ref.swiglu(gu).to(res.dtype)
     lib = require_lib()
     r2 = res.contiguous().view(M, K)
     if out is None:
@@ -897,6 +916,7 @@ def attn_decode_paged(q, k_pool, v_pool, block_table, pos, splits: int = 32,
                 vc[b, :, j * BS:(j + 1) * BS] = v_pool[blk]
         return ref.attn_decode(q, kc, vc, pos + 1, scale)
     lib = require_lib()
+    _check_gqa("attn_decode_paged", Hq, Hkv)
     if workspace is None:
         part_o = torch.empty(B, Hq, splits, D, dtype=torch.float32, device=q.device)
         part_ml = torch.empty(B, Hq, splits, 2, dtype=torch.float32, device=q.device)
@@ -969,14 +989,28 @@ def quant_fp8(w: torch.Tensor):
     return w8, scales
 
 
+def _gemv_fp8_ok(M: int, K: int) -> bool:
+    # k_gemv_*_fp8 are instantiated for M in {1,2,4,8} and stream 16 codes
+    # per load (nv = K >> 4): a K % 16 tail would be dropped
+    return M in (1, 2, 4, 8) and K % 16 == 0
+
+
+def _linear_fp8(x: torch.Tensor, w8: torch.Tensor,
+                wscale: torch.Tensor) -> torch.Tensor:
+    """x [..., K] @ dequant(w8, wscale)^T in f32, like the kernels: the dot
+    runs over the exact e4m3 values and the f32 row scale multiplies the
+    sum (rounding code*scale to bf16 first would cost 2^-9 per weight)."""
+    codes = w8.view(torch.float8_e4m3fn).float()
+    return torch.nn.functional.linear(x.float(), codes) * wscale.float()
+
+
 def gemv_norm_fp8(res, wnorm, w8, wscale, eps: float = 1e-5,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     M = res.numel() // res.shape[-1]
     K = res.shape[-1]
     N = w8.shape[0]
-    if not res.is_cuda:
-        w = ref.dequant_fp8(w8, wscale).to(res.dtype)
-        return torch.nn.functional.linear(rmsnorm(res, wnorm, eps), w)
+    if not res.is_cuda or not _gemv_fp8_ok(M, K):
+        return _linear_fp8(rmsnorm(res, wnorm, eps), w8, wscale).to(res.dtype)
     assert M * K * 2 <= 64 * 1024, \
         "fp8 norm-GEMV stages M*K bf16 activations in LDS (<=64 KB)"
     lib = require_lib()
@@ -992,10 +1026,9 @@ def gemv_res_fp8(x, w8, wscale, res) -> torch.Tensor:
     M = x.numel() // x.shape[-1]
     K = x.shape[-1]
     N = w8.shape[0]
-    if not x.is_cuda:
-        w = ref.dequant_fp8(w8, wscale).to(x.dtype)
-        lin = torch.nn.functional.linear(x, w)
-        res.copy_((res.float() + lin.float().view_as(res)).to(res.dtype))
+    if not x.is_cuda or not _gemv_fp8_ok(M, K):
+        lin = _linear_fp8(x, w8, wscale)
+        res.copy_((res.float() + lin.view_as(res)).to(res.dtype))
         return res
     lib = require_lib()
     x2 = x.contiguous().view(M, K)
@@ -1009,9 +1042,10 @@ def gemv_swiglu_norm_fp8(res, wnorm, w8, wscale, eps: float = 1e-5,
     M = res.numel() // res.shape[-1]
     K = res.shape[-1]
     I = w8.shape[0] // 2
-    if not res.is_cuda:
-        w = ref.dequant_fp8(w8, wscale).to(res.dtype)
-        return swiglu(torch.nn.functional.linear(rmsnorm(res, wnorm, eps), w))
+    if not res.is_cuda or not _gemv_fp8_ok(M, K):
+        # g/u stay f32 through silu, as in the kernel
+        gu = _linear_fp8(rmsnorm(res, wnorm, eps), w8, wscale)
+        return ref.swiglu(gu).to(res.dtype)
     assert M * K * 2 <= 64 * 1024
     lib = require_lib()
     r2 = res.contiguous().view(M, K)

@@ -213,7 +213,7 @@ void fei_attn_decode_fused(const void* q, const void* kin, const void* vin,
     case 2: LF(2); break;
     case 4: LF(4); break;
     case 8: LF(8); break;
-    default: break;   // wrapper validates
+    default: break;   // ops.attn_decode_fused raises ValueError before this
   }
 #undef LF
 }

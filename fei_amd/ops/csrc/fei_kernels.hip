@@ -655,7 +655,7 @@ void fei_attn_decode(const void* q, const void* k_cache, const void* v_cache,
     case 2: LAUNCH_DEC_R(2); break;
     case 4: LAUNCH_DEC_R(4); break;
     case 8: LAUNCH_DEC_R(8); break;
-    default: break;  // unsupported group size: wrapper validates
+    default: break;  // ops.attn_decode raises ValueError before this
   }
 #undef LAUNCH_DEC_R
 #undef LAUNCH_DEC
@@ -676,8 +676,10 @@ __global__ void k_attn_decode_combine(u16* __restrict__ out,
   const int d = threadIdx.x;
   __shared__ float sml[CMB_SMAX][2];
   const float* pml = part_ml + ((long)b * Hq + hq) * splits * 2;
-  if (d < 2 * splits)
-    ((float*)sml)[d] = pml[d];                    // parallel m/l fetch
+  // strided: D threads stage up to 2*CMB_SMAX values (D=64 with splits > 32
+  // needs two passes)
+  for (int i = d; i < 2 * splits; i += blockDim.x)
+    ((float*)sml)[i] = pml[i];                    // parallel m/l fetch
   __syncthreads();
   float m = -1.0f / 0.0f;
   for (int s = 0; s < splits; ++s) m = fmaxf(m, sml[s][0]);
@@ -1274,7 +1276,7 @@ void fei_attn_decode_paged(const void* q, void* k_pool,
     case 2: LPR(2); break;
     case 4: LPR(4); break;
     case 8: LPR(8); break;
-    default: break;
+    default: break;  // ops.attn_decode_paged raises ValueError before this
   }
 #undef LPR
 #undef LP

@@ -121,7 +121,7 @@ void fei_gemv(void* out, const void* x, const void* w, int M, int N, int K,
     case 2: LGD(2); break;
     case 4: LGD(4); break;
     case 8: LGD(8); break;
-    default: break;   // wrapper validates
+    default: break;   // ops.linear_decode routes other M to torch (_gemv_ok)
   }
 #undef LGD
 #undef LG

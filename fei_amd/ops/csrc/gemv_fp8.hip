@@ -251,6 +251,8 @@ k_quant_fp8_rows(unsigned char* __restrict__ w8, float* __restrict__ wscale,
 
 extern "C" {
 
+// other M (and K % 16 != 0, which nv = K >> 4 would truncate) never get
+// here: the ops.gemv_*_fp8 wrappers take their dequantise + linear path
 #define DISPATCH_M8(FN) \
   switch (M) { case 1: FN(1); break; case 2: FN(2); break; \
                case 4: FN(4); break; case 8: FN(8); break; default: break; }
