@@ -217,9 +217,13 @@ void fei_rope_kv_prefill(void* q, const void* k, const void* v, void* k_cache,
 // Grid (splits, Hkv, B), block 256 = 4 waves. One block serves ALL G=Hq/Hkv
 // q-heads of its kv-head, so each K/V row is read ONCE per block (the
 // one-block-per-q-head version re-read K/V G times — profiles/r01).
+// A split of 64 keys or more (chunk >= DEC_SHORT) runs tile by tile:
 //   phase A: thread-per-key; dot against the G q-vectors staged in LDS,
 //            G-wide block online-softmax state
-//   phase B: threads as (D/2 pairs x key-groups) accumulate P*V for all G
+//   phase B: threads as (D/8 row vectors x key-groups) accumulate P*V for
+//            all G
+// A shorter split runs attn_short_chunk (one pass, K and V on the phase-B
+// lane map, softmax inside a wave). The choice is per workgroup.
 // Partials: part_o [B,Hq,splits,D] f32; part_ml [B,Hq,splits,2] f32.
 // ---------------------------------------------------------------------------
 #define DEC_TILE 256
@@ -257,11 +261,12 @@ __device__ __forceinline__ void block_reduce_vec(float* v,
 }
 
 // ROPE=true additionally fuses the per-step RoPE + KV-append: q is the RAW
-// qkv-buffer view (roped into LDS during staging), the new token's k/v are
-// roped in-block from kin/vin (every split computes them — the new key may
-// fall in any split's chunk) and the split that OWNS key n-1 writes the
-// caches. Readers never read cache[n-1]; they use the LDS copy, so there is
-// no cross-workgroup ordering (placement-independent by construction).
+// qkv-buffer view (roped into LDS during staging) and the split that OWNS
+// key n-1 ropes the new token's k/v from kin/vin and writes the cache row.
+// No other split's [start,end) touches that row, so there is no
+// cross-workgroup ordering (placement-independent by construction). The
+// tiled path reads the row back after its barrier (same-workgroup
+// store->load); the short-chunk path uses an LDS copy instead.
 // sc1 write-through hand-off helpers for the fused split-K combine (guide
 // §6 G16 cheap variant): relaxed agent-scope stores/loads lower to sc1 at
 // 4-8 B widths — visibility comes from the write-through to the coherence
@@ -283,6 +288,222 @@ __device__ inline void store_i_sc1(int* p, int v) {
 }
 __device__ inline int load_i_sc1(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Stage the G q-vectors of this kv-head, scaled (ROPE: roped at p_new
+// first), into qs. No barrier.
+template <int G, bool ROPE>
+__device__ __forceinline__ void stage_q(float (*qs)[DEC_DMAX],
+                                        const u16* __restrict__ q,
+                                        const float* __restrict__ cos_sin,
+                                        int b, int hkv, int D, int p_new,
+                                        float scale, long q_bs) {
+  const int tid = threadIdx.x;
+  if (ROPE) {
+    const int half = D / 2;
+    for (int i = tid; i < G * half; i += blockDim.x) {
+      const int g = i / half, d = i % half;
+      const float c = cos_sin[((long)p_new * half + d) * 2 + 0];
+      const float sn = cos_sin[((long)p_new * half + d) * 2 + 1];
+      const u16* qp = q + (long)b * q_bs + (long)(hkv * G + g) * D;
+      const float x1 = bf2f(qp[d]);
+      const float x2 = bf2f(qp[d + half]);
+      qs[g][d] = (x1 * c - x2 * sn) * scale;
+      qs[g][d + half] = (x2 * c + x1 * sn) * scale;
+    }
+  } else {
+    for (int i = tid; i < G * D; i += blockDim.x) {
+      const int g = i / D, d = i % D;
+      qs[g][d] = bf2f(q[(long)b * q_bs + (long)(hkv * G + g) * D + d]) * scale;
+    }
+  }
+}
+
+// One-pass path of k_attn_decode for a split of fewer than DEC_SHORT keys
+// (always a single tile; the default 32 splits give 18-25 keys at the
+// benchmark's context). Every sum is taken in the order of the tiled
+// path's single-tile case (score: one fmaf chain over d = 0..D-1 per key;
+// l: xor butterfly 32..1 over the key lanes; P*V: one fmaf chain over the
+// keys per output, in segments of D/2 keys), so the partials are the same
+// bits a tile-by-tile pass would write — only the schedule differs:
+//   1. all 256 threads request the chunk's K and V rows up front (a row is
+//      covered by dvecs = D/8 adjacent lanes, 16 B each, coalesced;
+//      lane-group kg owns keys kg + s * kgroups, s < DEC_SLOTS: at most 4
+//      rows per group at D=128, 2 at D=64) together with the q / cos-sin
+//      loads: one memory round trip. Rows beyond the chunk are never
+//      requested (they may hold anything, NaN included).
+//   2. K rows go to an LDS tile ([key][D] bf16, 16-byte columns xor-
+//      swizzled by the row so that a column read over rows and a row read
+//      over columns are both conflict-free); barrier.
+//   3. scores: lane = key, wave = q head (two heads per wave at G=8); max,
+//      exp and sum stay inside the wave; p to ps[g][key], m and l straight
+//      to part_ml; barrier.
+//   4. the V rows, still in registers, replace K in the tile; barrier.
+//   5. P*V: thread = (head, d-pair), walks the keys in the tile and stores
+//      its two part_o values — no cross-thread reduction.
+// RoPE-fused form: the split that owns key p_new = n-1 (always its last
+// key) ropes it, writes the cache row, puts the K row into the tile and
+// keeps the V row in LDS; it never reads the cache row it writes. A split
+// holding ONLY p_new requests no cache row at all.
+#define DEC_SHORT 64
+#define DEC_SLOTS 4
+
+template <int G, bool ROPE, bool KVNT>
+__device__ __forceinline__ void attn_short_chunk(
+    const u16* __restrict__ q, u16* __restrict__ kc, u16* __restrict__ vc,
+    float* __restrict__ part_o, float* __restrict__ part_ml,
+    int b, int hkv, int split, int n, int start, int end,
+    int Hq, int Hkv, int D, int max_seq, int splits, float scale, long q_bs,
+    const u16* __restrict__ kin, const u16* __restrict__ vin,
+    const float* __restrict__ cos_sin, long kv_bs, bool sc1,
+    float (*qs)[DEC_DMAX], float (*ps)[DEC_SHORT], u16* tile, u16* newv) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int dvecs = D / 8;
+  const int swz = dvecs - 1;                      // column swizzle mask
+  const int kgroups = blockDim.x / dvecs;
+  const int dv = tid % dvecs;
+  const int kg = tid / dvecs;
+  const int nkeys = end - start;                  // 1 .. DEC_SHORT-1
+  const int p_new = n - 1;
+  const bool own = ROPE && end == n;              // p_new is our last key
+  const int nload = own ? nkeys - 1 : nkeys;      // keys read from the cache
+  const u16* kbase = kc + ((long)b * Hkv + hkv) * max_seq * D;
+  const u16* vbase = vc + ((long)b * Hkv + hkv) * max_seq * D;
+  s16x8* tile8 = (s16x8*)tile;
+
+  // slot guards are workgroup-uniform and the trip count is fixed, so all
+  // requests are in flight before the first wait
+  s16x8 kr[DEC_SLOTS], vr[DEC_SLOTS];
+#pragma unroll
+  for (int s = 0; s < DEC_SLOTS; ++s) {
+    kr[s] = (s16x8)(0);
+    vr[s] = (s16x8)(0);
+    if (s * kgroups < nload) {
+      const int j = kg + s * kgroups;
+      const long row = start + (j < nload ? j : 0);
+      const s16x8* kp = (const s16x8*)(kbase + row * D) + dv;
+      const s16x8* vp = (const s16x8*)(vbase + row * D) + dv;
+      kr[s] = KVNT ? __builtin_nontemporal_load(kp) : *kp;
+      vr[s] = KVNT ? __builtin_nontemporal_load(vp) : *vp;
+    }
+  }
+
+  stage_q<G, ROPE>(qs, q, cos_sin, b, hkv, D, p_new, scale, q_bs);
+#pragma unroll
+  for (int s = 0; s < DEC_SLOTS; ++s) {
+    if (s * kgroups < nload) {
+      const int j = kg + s * kgroups;
+      if (j < nload) tile8[j * dvecs + (dv ^ (j & swz))] = kr[s];
+    }
+  }
+  if (own) {
+    const int half = D / 2;
+    const int r = nkeys - 1;                      // tile row of the new key
+    u16* kcp = kc + (((long)b * Hkv + hkv) * max_seq + p_new) * D;
+    u16* vcp = vc + (((long)b * Hkv + hkv) * max_seq + p_new) * D;
+    for (int d = tid; d < half; d += blockDim.x) {
+      const float c = cos_sin[((long)p_new * half + d) * 2 + 0];
+      const float sn = cos_sin[((long)p_new * half + d) * 2 + 1];
+      const u16* kp = kin + (long)b * kv_bs + (long)hkv * D;
+      const u16* vp = vin + (long)b * kv_bs + (long)hkv * D;
+      const float x1 = bf2f(kp[d]);
+      const float x2 = bf2f(kp[d + half]);
+      const u16 k1 = f2bf(x1 * c - x2 * sn);
+      const u16 k2 = f2bf(x2 * c + x1 * sn);
+      const u16 v1 = vp[d], v2 = vp[d + half];
+      kcp[d] = k1;
+      kcp[d + half] = k2;
+      vcp[d] = v1;
+      vcp[d + half] = v2;
+      const int d2 = d + half;
+      tile[(r * dvecs + ((d >> 3) ^ (r & swz))) * 8 + (d & 7)] = k1;
+      tile[(r * dvecs + ((d2 >> 3) ^ (r & swz))) * 8 + (d2 & 7)] = k2;
+      newv[d] = v1;
+      newv[d2] = v2;
+    }
+  }
+  __syncthreads();                                // qs, K tile, newv
+
+  if (own) {
+#pragma unroll
+    for (int s = 0; s < DEC_SLOTS; ++s) {
+      if (kg + s * kgroups == nkeys - 1) vr[s] = ((const s16x8*)newv)[dv];
+    }
+  }
+
+  // scores and softmax statistics: lane = key, wave = head
+#pragma unroll
+  for (int hh = 0; hh < (G + 3) / 4; ++hh) {
+    const int g = w + 4 * hh;
+    if (g < G) {                                  // wave-uniform
+      float sc = -1.0f / 0.0f;
+      if (lane < nkeys) {
+        sc = 0.f;
+        const s16x8* krow = tile8 + lane * dvecs;
+        for (int i = 0; i < dvecs; ++i) {
+          const s16x8 k8 = krow[i ^ (lane & swz)];
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            sc = fmaf(qs[g][i * 8 + j], bf2f((u16)k8[j]), sc);
+        }
+      }
+      const float mx = wave_reduce_max(sc);
+      const float pv = lane < nkeys ? __expf(sc - mx) : 0.f;
+      ps[g][lane] = pv;
+      float l = pv;
+#pragma unroll
+      for (int off = 32; off; off >>= 1) l = l + __shfl_xor(l, off);
+      if (lane == 0) {
+        float* pml =
+            part_ml + (((long)b * Hq + hkv * G + g) * splits + split) * 2;
+        if (sc1) store2_sc1(pml, mx, l);
+        else { pml[0] = mx; pml[1] = l; }
+      }
+    }
+  }
+  __syncthreads();                                // ps; K tile is dead
+
+#pragma unroll
+  for (int s = 0; s < DEC_SLOTS; ++s) {
+    if (s * kgroups < nkeys) {
+      const int j = kg + s * kgroups;
+      if (j < nkeys) tile8[j * dvecs + (dv ^ (j & swz))] = vr[s];
+    }
+  }
+  __syncthreads();                                // V tile
+
+  // P*V: thread = (head, d-pair); the keys in segments of D/2, each summed
+  // from zero, then added in order
+  const int dpairs = D / 2;
+  const u32* tile32 = (const u32*)tile;
+#pragma unroll
+  for (int r = 0; r < (G * (DEC_DMAX / 2) + 255) / 256; ++r) {
+    const int pi = tid + 256 * r;
+    if (pi < G * dpairs) {
+      const int g = pi / dpairs, dp = pi % dpairs;
+      const int c = dp >> 2, e = dp & 3;          // 4 pairs per 16-B column
+      float o0 = 0.f, o1 = 0.f;
+      for (int j0 = 0; j0 < nkeys; j0 += dpairs) {
+        const int j1 = min(nkeys, j0 + dpairs);
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll 4
+        for (int j = j0; j < j1; ++j) {
+          const u32 vpair = tile32[(j * dvecs + (c ^ (j & swz))) * 4 + e];
+          const float p = ps[g][j];
+          a0 = fmaf(p, bf2f((u16)(vpair & 0xffff)), a0);
+          a1 = fmaf(p, bf2f((u16)(vpair >> 16)), a1);
+        }
+        if (j0 == 0) { o0 = a0; o1 = a1; }
+        else { o0 += a0; o1 += a1; }
+      }
+      float* po = part_o +
+          (((long)b * Hq + hkv * G + g) * splits + split) * D + dp * 2;
+      if (sc1) store2_sc1(po, o0, o1);
+      else { po[0] = o0; po[1] = o1; }
+    }
+  }
 }
 
 // When `flags` is non-null the split-K combine is FUSED: every split
@@ -314,11 +535,17 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
   const int tid = threadIdx.x;
 
   __shared__ float qs[DEC_GMAX][DEC_DMAX];
-  __shared__ float pl[DEC_GMAX][DEC_TILE];
+  // pl [DEC_GMAX][DEC_TILE] and, behind it, the key-group partial-o staging
+  // osh [kg * dvecs + dv][element] (kgroups * dvecs == blockDim == DEC_TILE
+  // for every D) are one 16 KB block: the short-chunk path uses it whole
+  // as its K / V tile (63 rows x 256 B)
+  __shared__ __attribute__((aligned(16))) float plosh[(DEC_GMAX + 8) * DEC_TILE];
+  float (*pl)[DEC_TILE] = (float (*)[DEC_TILE])plosh;
+  float (*osh)[8] = (float (*)[8])(plosh + DEC_GMAX * DEC_TILE);
   __shared__ float red[DEC_GMAX][4];
-  // key-group partial-o staging: [kg * dvecs + dv][element] — kgroups *
-  // dvecs == blockDim == DEC_TILE for every D
-  __shared__ float osh[DEC_TILE][8];
+  // short-chunk path: p per (head, key); the new token's V row
+  __shared__ float ps[DEC_GMAX][DEC_SHORT];
+  __shared__ __attribute__((aligned(16))) u16 newv[DEC_DMAX];
 
   const int n = pos[b] + 1;
   const int chunk = (n + splits - 1) / splits;
@@ -341,22 +568,19 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
       }
     }
     if (arrive == nullptr) return;
+  } else if (chunk < DEC_SHORT) {
+    // workgroup-uniform: chunk depends on pos[b] only, so sequences of one
+    // launch may sit on either side
+    attn_short_chunk<G, ROPE, KVNT>(
+        q, kc, vc, part_o, part_ml, b, hkv, split, n, start, end, Hq, Hkv, D,
+        max_seq, splits, scale, q_bs, kin, vin, cos_sin, kv_bs,
+        arrive != nullptr, qs, ps, (u16*)plosh, newv);
   } else {
 
   const int half = D / 2;
   const int p_new = n - 1;
+  stage_q<G, ROPE>(qs, q, cos_sin, b, hkv, D, p_new, scale, q_bs);
   if (ROPE) {
-    // stage roped+scaled q
-    for (int i = tid; i < G * half; i += blockDim.x) {
-      const int g = i / half, d = i % half;
-      const float c = cos_sin[((long)p_new * half + d) * 2 + 0];
-      const float sn = cos_sin[((long)p_new * half + d) * 2 + 1];
-      const u16* qp = q + (long)b * q_bs + (long)(hkv * G + g) * D;
-      const float x1 = bf2f(qp[d]);
-      const float x2 = bf2f(qp[d + half]);
-      qs[g][d] = (x1 * c - x2 * sn) * scale;
-      qs[g][d + half] = (x2 * c + x1 * sn) * scale;
-    }
     // the split whose chunk contains key p_new ropes + appends the new
     // token's k/v BEFORE this block's barrier, then reads it back from the
     // cache like any other key (same-workgroup store->load visibility).
@@ -377,35 +601,22 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
         vcp[d + half] = vp[d + half];
       }
     }
-  } else {
-    // q pre-roped; stage scaled
-    for (int i = tid; i < G * D; i += blockDim.x) {
-      const int g = i / D, d = i % D;
-      qs[g][d] = bf2f(q[(long)b * q_bs + (long)(hkv * G + g) * D + d]) * scale;
-    }
   }
   __syncthreads();
 
   const u16* kbase = kc + ((long)b * Hkv + hkv) * max_seq * D;
   const u16* vbase = vc + ((long)b * Hkv + hkv) * max_seq * D;
 
-  // V pass lane maps. WIDE (chunk >= 64): 16 B of one V row per lane —
-  // fewer, full-width loads win once every key-group has work (+1% at
-  // 2k-8k context). PAIR (short chunks): 4 B per lane over D/2 lanes —
-  // 4x more active lanes when the chunk covers few keys (the wide map
-  // measured -3% on the 512-ctx headline: only 16 of 256 lanes active).
-  // Ablation: experimental/decode_ablate.hip, profiles/r02.
+  // V pass lane map (chunk >= DEC_SHORT; shorter chunks took the one-pass
+  // path above): 16 B of one V row per lane, dvecs lanes per row, kgroups
+  // rows at a time — full-width loads once every key-group has work (+1%
+  // at 2k-8k context over a 4 B-per-lane map). Ablation:
+  // experimental/decode_ablate.hip, profiles/r02.
   const int dvecs = D / 8;                        // 16 for D=128
   const int kgroups = blockDim.x / dvecs;         // 16
   const int keys_per_group = DEC_TILE / kgroups;  // 16
   const int dv = tid % dvecs;
   const int kg = tid / dvecs;
-  const bool wide = chunk >= 64;
-  const int dpairs = D / 2;                       // pair-mode roles
-  const int kgroupsP = blockDim.x / dpairs;
-  const int keysP = DEC_TILE / kgroupsP;
-  const int dp = tid % dpairs;
-  const int kgP = tid / dpairs;
 
   float m[DEC_GMAX], l[DEC_GMAX], sc[DEC_GMAX];
   float oa[DEC_GMAX][8];
@@ -470,7 +681,7 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
     // in flight (a data-dependent break serialises the loop into dependent
     // L2 round trips — measured 41 us/kernel at seq 640).
     const int kmax = min(DEC_TILE, end - tile);
-    if (wide) {
+    {
       const int kbase_local = kg * keys_per_group;
       const int iters = min(keys_per_group, max(0, kmax - kbase_local));
 #pragma unroll 2
@@ -489,25 +700,6 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
           for (int e = 0; e < 8; ++e) oa[g][e] = fmaf(p, vf[e], oa[g][e]);
         }
       }
-    } else {
-      const int kbase_local = kgP * keysP;
-      const int iters = min(keysP, max(0, kmax - kbase_local));
-#pragma unroll 4
-      for (int j = 0; j < iters; ++j) {
-        const int kl = kbase_local + j;
-        const u16* vrow = vbase + (long)(tile + kl) * D + dp * 2;
-        const u32 vpair = KVNT
-            ? __builtin_nontemporal_load((const u32*)vrow)
-            : *(const u32*)vrow;
-        const float v0 = bf2f((u16)(vpair & 0xffff));
-        const float v1 = bf2f((u16)(vpair >> 16));
-        #pragma unroll
-    for (int g = 0; g < G; ++g) {
-          const float p = pl[g][kl];
-          oa[g][0] = fmaf(p, v0, oa[g][0]);
-          oa[g][1] = fmaf(p, v1, oa[g][1]);
-        }
-      }
     }
     __syncthreads();                               // pl reuse next tile
   }
@@ -520,7 +712,7 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
     const int hq = hkv * G + g;
     float* po = part_o + (((long)b * Hq + hq) * splits + split) * D;
     float* pml = part_ml + (((long)b * Hq + hq) * splits + split) * 2;
-    if (wide) {
+    {
 #pragma unroll
       for (int e = 0; e < 8; ++e) osh[kg * dvecs + dv][e] = oa[g][e];
       __syncthreads();
@@ -540,19 +732,6 @@ k_attn_decode(const u16* __restrict__ q, u16* __restrict__ kc,
 #pragma unroll
           for (int e = 0; e < 8; ++e) po[dv * 8 + e] = s[e];
         }
-      }
-    } else {
-      osh[kgP * dpairs + dp][0] = oa[g][0];
-      osh[kgP * dpairs + dp][1] = oa[g][1];
-      __syncthreads();
-      if (kgP == 0) {
-        float s0 = osh[dp][0], s1 = osh[dp][1];
-        for (int gg = 1; gg < kgroupsP; ++gg) {
-          s0 += osh[gg * dpairs + dp][0];
-          s1 += osh[gg * dpairs + dp][1];
-        }
-        if (arrive != nullptr) store2_sc1(&po[dp * 2], s0, s1);
-        else { po[dp * 2] = s0; po[dp * 2 + 1] = s1; }
       }
     }
     if (tid == 0) {
@@ -1104,8 +1283,9 @@ k_attn_decode_paged(const u16* __restrict__ q, u16* __restrict__ kp,
   }
   __syncthreads();
 
-  // chunk-adaptive V lane maps — same scheme as k_attn_decode (wide
-  // 16 B/lane once a split's chunk covers >= 64 keys; pair otherwise)
+  // chunk-adaptive V lane maps: wide (16 B/lane, as in k_attn_decode)
+  // once a split's chunk covers >= 64 keys; pair (4 B/lane over D/2
+  // lanes) otherwise — this kernel has no one-pass short-chunk path yet
   const int dvecs = D / 8;
   const int kgroups = blockDim.x / dvecs;
   const int keys_per_group = DEC_TILE / kgroups;
