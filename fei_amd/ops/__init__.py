@@ -186,9 +186,19 @@ def _check_gqa(name: str, Hq: int, Hkv: int) -> None:
                          "(Hq/Hkv must be 1, 2, 4 or 8)")
 
 
+def _check_vec8(name: str, n: int, what: str = "last dimension") -> None:
+    """The row-wise and element-wise kernels move 8 bf16 per lane and size
+    their loops as n >> 3: a tail of n % 8 elements would stay unwritten."""
+    if n % 8 != 0:
+        raise ValueError(f"{name}: {what} must be a multiple of 8, got {n}")
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """RMSNorm over the last dim. x: [..., C] bf16 (GPU) / any float (CPU)."""
+    _check_vec8("rmsnorm", x.shape[-1])
+    if x.numel() == 0:                  # zero rows: an empty grid is an error
+        return torch.empty_like(x) if out is None else out
     if not x.is_cuda:
         return ref.rmsnorm(x, weight, eps)
     lib = require_lib()
@@ -206,6 +216,15 @@ def fused_add_rmsnorm(x: torch.Tensor, residual: torch.Tensor,
                       out: Optional[torch.Tensor] = None
                       ) -> Tuple[torch.Tensor, torch.Tensor]:
     """residual += x (in place on GPU); out = rmsnorm(residual)."""
+    _check_vec8("fused_add_rmsnorm", x.shape[-1])
+    # the kernel updates residual through its raw pointer, row r at r * cols:
+    # a strided view would be read and written at the wrong addresses, and a
+    # contiguous copy would lose the in-place update
+    if not residual.is_contiguous():
+        raise ValueError("fused_add_rmsnorm: residual must be contiguous "
+                         "(it is updated in place)")
+    if x.numel() == 0:
+        return (torch.empty_like(x) if out is None else out), residual
     if not x.is_cuda:
         o, res = ref.fused_add_rmsnorm(x, residual, weight, eps)
         residual.copy_(res)
@@ -453,18 +472,33 @@ def attn_prefill(q, k_cache, v_cache, pos0, scale: Optional[float] = None,
     kv8 = _kv8_pair(k_cache, v_cache)
     if kv8 and not causal:
         raise ValueError("fp8 KV prefill attention is causal-only")
+    Hkv = k_cache.shape[1]
+    # the kernels index the cache with hkv = hq / (Hq / Hkv): a group that is
+    # not integral reaches hkv = Hkv, one head past the cache (any integral
+    # group is fine: the prefill kernels are not templated on it)
+    if Hkv <= 0 or Hq % Hkv != 0:
+        raise ValueError(f"attn_prefill: Hq={Hq} is not a multiple of "
+                         f"Hkv={Hkv}")
     if not q.is_cuda:
         if kv8:
             n = int(pos0.max()) + S
-            return ref.attn_prefill(q, k_cache.dequant(n), v_cache.dequant(n),
-                                    pos0, scale)
+            kd, vd = k_cache.dequant(n), v_cache.dequant(n)
+            if q.dtype == torch.bfloat16:
+                # bf16 run: the kernel stages bf16(f32(code) * scale)
+                kd, vd = kd.to(q.dtype), vd.to(q.dtype)
+            return ref.attn_prefill(q, kd, vd, pos0, scale)
         if causal:
             return ref.attn_prefill(q, k_cache, v_cache, pos0, scale)
         # bidirectional reference: softmax over [0, kv_len)
         return _ref_bidir(q, k_cache, v_cache, kv_len, scale)
     lib = require_lib()
+    # k_attn_prefill / k_attn_prefill_kv8 are instantiated for these two head
+    # sizes; the bf16 C entry point launches nothing for any other and the
+    # output would be uninitialised memory
+    if D not in (64, 128):
+        raise ValueError(f"attn_prefill supports D in (64,128), got {D}")
     if out is None:
-        out = torch.empty_like(q)
+        out = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
     if kv8:
         assert q.stride(3) == 1 and q.stride(2) == D
         assert q.stride(0) == S * q.stride(1)
@@ -480,7 +514,6 @@ def attn_prefill(q, k_cache, v_cache, pos0, scale: Optional[float] = None,
         return out
     if kv_len is None:
         kv_len = pos0  # unused when causal
-    Hkv = k_cache.shape[1]
     assert q.stride(3) == 1 and q.stride(2) == D
     assert q.stride(0) == S * q.stride(1)
     assert out.is_contiguous()
@@ -511,11 +544,18 @@ def _ref_bidir(q, k_cache, v_cache, kv_len, scale):
 def swiglu(gate_up: torch.Tensor,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gate_up [..., 2*inter] -> [..., inter]: silu(gate) * up."""
+    inter = gate_up.shape[-1] // 2
+    if gate_up.shape[-1] != 2 * inter:
+        raise ValueError("swiglu: the last dimension must be even, got "
+                         f"{gate_up.shape[-1]}")
+    _check_vec8("swiglu", inter, "inter")
+    if gate_up.numel() == 0:
+        return gate_up.new_empty(*gate_up.shape[:-1], inter) \
+            if out is None else out
     if not gate_up.is_cuda:
         return ref.swiglu(gate_up)
     lib = require_lib()
     gu = gate_up.contiguous()
-    inter = gu.shape[-1] // 2
     rows = gu.numel() // gu.shape[-1]
     if out is None:
         out = torch.empty(*gu.shape[:-1], inter, dtype=gu.dtype, device=gu.device)
@@ -766,7 +806,10 @@ def gemv_swiglu(x: torch.Tensor, wgu: torch.Tensor,
     M = x.numel() // x.shape[-1]
     K = x.shape[-1]
     I = wgu.shape[0] // 2
-    if not x.is_cuda or not (_gemv_ok(M, K) or _gemm_m8_ok(M, 2 * I, K)):
+    if not x.is_cuda:
+        # the reference has no vector width: any I
+        return ref.swiglu(torch.nn.functional.linear(x, wgu))
+    if not (_gemv_ok(M, K) or _gemm_m8_ok(M, 2 * I, K)):
         return swiglu(torch.nn.functional.linear(x, wgu))
     lib = require_lib()
     x2 = x.contiguous().view(M, K)
@@ -949,6 +992,9 @@ def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
               eps: float = 1e-5, residual: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """LayerNorm of (x [+ residual]) over the last dim (encoder blocks)."""
+    _check_vec8("layernorm", x.shape[-1])
+    if x.numel() == 0:
+        return torch.empty_like(x) if out is None else out
     if not x.is_cuda:
         return ref.layernorm(x, weight, bias, eps, residual)
     lib = require_lib()
@@ -964,6 +1010,10 @@ def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
 
 
 def gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact (erf) GELU, element-wise."""
+    _check_vec8("gelu", x.numel(), "element count")
+    if x.numel() == 0:
+        return torch.empty_like(x) if out is None else out
     if not x.is_cuda:
         return ref.gelu(x)
     lib = require_lib()
