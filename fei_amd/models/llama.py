@@ -235,8 +235,30 @@ class LlamaModel:
         scale = 1.0 / math.sqrt(self.D)
         n_layers = len(self.layers)
         x = ops.rmsnorm(h, self.layers[0].norm_attn, s.norm_eps)
+        # Batch 1 on one GPU: the add+norm in front of the gate/up GEMV and
+        # of the next layer's qkv GEMV runs as that GEMV's prologue
+        # (ops.gemv_addnorm; bit-identical, FEI_ADDNORM_GEMV=0 restores the
+        # launches). The kernel cannot update the residual in place, so it
+        # ping-pongs between two buffers; two fused norms per layer keep the
+        # parity the same every step, so one captured graph stays valid.
+        # The norm before lm_head stays a launch: 16k workgroups would each
+        # repeat the prologue to save one 4.6 us kernel per step.
+        addnorm = (ops._ADDNORM_GEMV and self.tp_size == 1 and B == 1
+                   and h.is_cuda and h.dtype == torch.bfloat16
+                   and ops._addnorm_ok(B, s.hidden_size))
+        if addnorm:
+            h = h.contiguous()
+            hb = torch.empty(2, B, s.hidden_size, dtype=h.dtype,
+                             device=h.device)
+            nbuf = 0
+        d = None
         for li, lw in enumerate(self.layers):
-            qkv = ops.linear_decode(x, lw.wqkv)
+            if addnorm and li > 0:
+                qkv = ops.gemv_addnorm(d, h, hb[nbuf], lw.norm_attn, lw.wqkv,
+                                       s.norm_eps)
+                h, nbuf = hb[nbuf], nbuf ^ 1
+            else:
+                qkv = ops.linear_decode(x, lw.wqkv)
             q, k, v = self._qkv_views(qkv, B)
             if fused_attn:
                 att = ops.attn_decode_fused(q, k, v, k_caches[li],
@@ -250,10 +272,17 @@ class LlamaModel:
                                       k=k, v=v, table=self.rope, layer=li)
             o = ops.linear_decode(att.reshape(B, -1), lw.wo)
             all_reduce_sum(o, self.tp)
-            x, h = ops.fused_add_rmsnorm(o, h, lw.norm_mlp, s.norm_eps)
-            act = ops.gemv_swiglu(x, lw.wgu)
+            if addnorm:
+                act = ops.gemv_swiglu_addnorm(o, h, hb[nbuf], lw.norm_mlp,
+                                              lw.wgu, s.norm_eps)
+                h, nbuf = hb[nbuf], nbuf ^ 1
+            else:
+                x, h = ops.fused_add_rmsnorm(o, h, lw.norm_mlp, s.norm_eps)
+                act = ops.gemv_swiglu(x, lw.wgu)
             d = ops.linear_decode(act, lw.wdown)
             all_reduce_sum(d, self.tp)
+            if addnorm and li + 1 < n_layers:
+                continue                  # folded into the next layer's qkv
             next_norm = (self.layers[li + 1].norm_attn if li + 1 < n_layers
                          else self.norm_f)
             x, h = ops.fused_add_rmsnorm(d, h, next_norm, s.norm_eps)

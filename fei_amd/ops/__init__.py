@@ -104,6 +104,10 @@ def _try_load() -> None:
                                   _vp]
     lib.fei_gemv_swiglu_norm.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _f,
                                          _i, _vp, _vp]
+    for fn in (lib.fei_gemv_addnorm, lib.fei_gemv_swiglu_addnorm):
+        fn.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i,
+                       _vp]
+        fn.restype = _i
     _LIB = lib
 
 
@@ -760,6 +764,13 @@ _GEMV_NT_MIN_BYTES = int(os.environ.get("FEI_GEMV_NT_MIN", 0))
 # 4-protocol measurement ladder is profiles/r02_fused_combine.md).
 # Opt-in via FEI_FUSED_CMB=1; the launch form stays the default.
 _FUSED_CMB = os.environ.get("FEI_FUSED_CMB", "0") == "1"
+# Batch-1 plain decode chain: run the residual add + RMSNorm in front of the
+# gate/up and qkv GEMVs as those GEMVs' prologue (gemv_addnorm /
+# gemv_swiglu_addnorm, bit-identical to the launches they replace) instead
+# of 63 single-workgroup k_add_rmsnorm launches per step. FEI_ADDNORM_GEMV=0
+# restores the launches for A/B inside one build
+# (profiles/gemv_addnorm.md).
+_ADDNORM_GEMV = os.environ.get("FEI_ADDNORM_GEMV", "1") == "1"
 
 
 def _gemm_m8_ok(M: int, N: int, K: int) -> bool:
@@ -903,6 +914,102 @@ def gemv_swiglu_norm(res: torch.Tensor, wnorm: torch.Tensor,
                              M, I, K, eps, nt,
                              _ptr(ssq) if ssq is not None else None,
                              _stream())
+    return out
+
+
+# -- residual add + RMSNorm folded into the consuming GEMV -------------------
+
+# Row groups one workgroup walks behind a single add+norm prologue (a group
+# is 8 rows in gemv_addnorm, 4 in gemv_swiglu_addnorm). Pure scheduling: a
+# row's sum does not depend on which workgroup owns it.
+# FEI_ADDNORM_RG / FEI_ADDNORM_RG_SWIGLU override (profiles/gemv_addnorm.md).
+_ADDNORM_ROW_GROUPS = max(1, int(os.environ.get("FEI_ADDNORM_RG", "2") or 2))
+_ADDNORM_ROW_GROUPS_SWIGLU = max(
+    1, int(os.environ.get("FEI_ADDNORM_RG_SWIGLU", "2") or 2))
+
+
+def _addnorm_ok(M: int, K: int) -> bool:
+    # batch 1 only, and the normalised row is staged in LDS (32 KB cap, the
+    # one forward_decode uses for the norm-prologue chain)
+    return M == 1 and _gemv_ok(M, K) and M * K * 2 <= 32 * 1024
+
+
+def _addnorm_check(name: str, delta, res_in, res_out) -> None:
+    if not res_in.is_contiguous() or not res_out.is_contiguous():
+        raise ValueError(f"{name}: res_in and res_out must be contiguous")
+    if res_in.shape != res_out.shape or res_in.dtype != res_out.dtype:
+        raise ValueError(f"{name}: res_in and res_out must match in shape "
+                         "and dtype")
+    if delta.shape != res_in.shape:
+        raise ValueError(f"{name}: delta must have the residual's shape")
+    # every workgroup reads res_in while one of them writes res_out: the two
+    # may not share storage, wholly or in part
+    a0, b0 = res_in.data_ptr(), res_out.data_ptr()
+    nbytes = res_in.numel() * res_in.element_size()
+    if a0 < b0 + nbytes and b0 < a0 + nbytes:
+        raise ValueError(f"{name}: res_in and res_out must not share storage "
+                         "(the new residual cannot be written in place)")
+
+
+def gemv_addnorm(delta: torch.Tensor, res_in: torch.Tensor,
+                 res_out: torch.Tensor, wnorm: torch.Tensor, w: torch.Tensor,
+                 eps: float = 1e-5,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """res_out = res_in + delta; out = rmsnorm(res_out)*wnorm @ w^T in ONE
+    kernel at batch 1 — bit-identical to fused_add_rmsnorm followed by
+    linear_decode, which is also what every other shape and the CPU run
+    (through res_out; res_in is left untouched)."""
+    _addnorm_check("gemv_addnorm", delta, res_in, res_out)
+    K = res_in.shape[-1]
+    M = res_in.numel() // max(K, 1)
+    N = w.shape[0]
+    if not res_in.is_cuda or not _addnorm_ok(M, K):
+        res_out.copy_(res_in)
+        x, _ = fused_add_rmsnorm(delta, res_out, wnorm, eps)
+        return linear_decode(x, w, out=out)
+    lib = require_lib()
+    d2 = delta.contiguous()
+    if out is None:
+        out = torch.empty(*res_in.shape[:-1], N, dtype=res_in.dtype,
+                          device=res_in.device)
+    nt = 1 if (N * K * 2 >= _GEMV_NT_MIN_BYTES) else 0
+    rc = lib.fei_gemv_addnorm(_ptr(out), _ptr(d2), _ptr(res_in),
+                              _ptr(res_out), _ptr(wnorm), _ptr(w), M, N, K,
+                              eps, nt, _ADDNORM_ROW_GROUPS, _stream())
+    if rc != 0:
+        raise RuntimeError(f"fei_gemv_addnorm refused the launch (rc={rc})")
+    return out
+
+
+def gemv_swiglu_addnorm(delta: torch.Tensor, res_in: torch.Tensor,
+                        res_out: torch.Tensor, wnorm: torch.Tensor,
+                        wgu: torch.Tensor, eps: float = 1e-5,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """res_out = res_in + delta; out = silu(g)*u with [g;u] =
+    rmsnorm(res_out)*wnorm @ wgu^T in ONE kernel at batch 1 — bit-identical
+    to fused_add_rmsnorm followed by gemv_swiglu (the fallback for every
+    other shape and the CPU)."""
+    _addnorm_check("gemv_swiglu_addnorm", delta, res_in, res_out)
+    K = res_in.shape[-1]
+    M = res_in.numel() // max(K, 1)
+    I = wgu.shape[0] // 2
+    if not res_in.is_cuda or not _addnorm_ok(M, K):
+        res_out.copy_(res_in)
+        x, _ = fused_add_rmsnorm(delta, res_out, wnorm, eps)
+        return gemv_swiglu(x, wgu, out=out)
+    lib = require_lib()
+    d2 = delta.contiguous()
+    if out is None:
+        out = torch.empty(*res_in.shape[:-1], I, dtype=res_in.dtype,
+                          device=res_in.device)
+    nt = 1 if (wgu.shape[0] * K * 2 >= _GEMV_NT_MIN_BYTES) else 0
+    rc = lib.fei_gemv_swiglu_addnorm(_ptr(out), _ptr(d2), _ptr(res_in),
+                                     _ptr(res_out), _ptr(wnorm), _ptr(wgu),
+                                     M, I, K, eps, nt,
+                                     _ADDNORM_ROW_GROUPS_SWIGLU, _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_gemv_swiglu_addnorm refused the launch (rc={rc})")
     return out
 
 
