@@ -3,11 +3,14 @@
 Sized for MI355X's 288 GB HBM3E: the pool reserves a fraction of free GPU
 memory as fixed-size blocks; sequences map logical block indices to physical
 blocks so many agent sessions can share one engine without fragmentation.
-The flagship decode path uses contiguous per-sequence caches (the HIP
-decode-attention kernel reads [B,Hkv,max_seq,D]); this allocator manages
-*session* lifetimes above that: each session owns a contiguous region and
-the pool tracks free regions. (Block-table attention is a planned kernel
-extension; the allocator API already speaks blocks.)
+The flagship single-conversation path uses contiguous per-sequence caches
+([B,Hkv,max_seq,D]); the paged serving path (engine/sessions.py) keeps every
+session's KV in blocks of this pool and reads and writes them through a block
+table with the HIP kernels k_attn_decode_paged (decode, fused RoPE + append),
+k_rope_kv_prefill_paged and k_attn_prefill_paged (prefill and multi-turn
+continuation). The allocator is host-side bookkeeping only: blocks are
+handed out, grown (ensure_capacity), given back (truncate, release) and
+copied (fork); it never moves a row.
 """
 
 from __future__ import annotations
@@ -96,6 +99,26 @@ class PagedKVPool:
                     "sequence first")
             t.blocks.append(self._free.pop())
         t.length = max(t.length, n_tokens)
+        return t.blocks
+
+    def truncate(self, seq_id: int, n_tokens: int) -> List[int]:
+        """Shrink a sequence to n_tokens: the blocks beyond
+        ceil(n_tokens / block_size) go back to the free list — in the
+        reverse of the order ensure_capacity took them, so undoing a growth
+        leaves the free list as it was — and ``length`` becomes n_tokens.
+        Returns the remaining block list."""
+        if n_tokens < 0:
+            raise ValueError(f"n_tokens must be >= 0, got {n_tokens}")
+        t = self._tables[seq_id]
+        keep = (n_tokens + self.block_size - 1) // self.block_size
+        if keep > len(t.blocks):
+            raise ValueError(
+                f"truncate cannot grow a sequence ({len(t.blocks)} blocks "
+                f"held, {keep} asked); use ensure_capacity")
+        freed = t.blocks[keep:]
+        del t.blocks[keep:]
+        self._free.extend(reversed(freed))
+        t.length = n_tokens
         return t.blocks
 
     def release(self, seq_id: int) -> None:

@@ -7,6 +7,12 @@ leave the decode batch at any step, and the attention read path is the HIP
 block-table kernel (`k_attn_decode_paged`). Admission is explicit — a
 session that cannot get blocks raises and the caller can evict.
 
+Prompts are prefilled straight into the session's blocks
+(`LlamaModel.forward_prefill_paged`: `k_rope_kv_prefill_paged` +
+`k_attn_prefill_paged`), and a finished session can be continued with new
+prompt tokens (`extend`: a tool result, the next user message) without
+re-prefilling the conversation: open -> step -> result -> extend -> step ...
+
 Control-plane costs stay host-side (per-step RoPE/append scatter is a few
 microseconds of torch indexing per layer); the O(context) work — attention
 over the pool — is the paged HIP kernel, and all GEMVs take the same
@@ -40,6 +46,11 @@ class Session:
     pos: int = 0                     # current context length in the pool
     max_new_tokens: int = 256
     done: bool = False
+    turn: int = 0                    # 0 = the turn open() started
+    # everything in front of the current turn's tokens: prompt_ids, then for
+    # every finished turn its emitted tokens (EOS included) and the
+    # extension that followed
+    context_ids: List[int] = field(default_factory=list)
 
 
 class PagedSessionManager:
@@ -140,7 +151,6 @@ class PagedSessionManager:
         MemoryError when the pool has no blocks (caller evicts/queues)."""
         ids = (self.engine.tokenizer.encode(prompt)
                if isinstance(prompt, str) else list(prompt))
-        m, dev = self.model, self.model.device
         S = len(ids)
         sid = self.pool.new_sequence()
         try:
@@ -148,29 +158,86 @@ class PagedSessionManager:
         except MemoryError:
             self.pool.release(sid)
             raise
-        # prefill through the normal MFMA path into a contiguous scratch,
-        # then scatter each layer's S rows into this session's blocks
-        k_tmp = [torch.zeros(1, m.hkv_l, S, m.D, device=dev, dtype=m.dtype)
-                 for _ in range(m.spec.num_layers)]
-        v_tmp = [torch.zeros_like(k_tmp[0]) for _ in range(m.spec.num_layers)]
-        tokens = torch.tensor([ids], dtype=torch.int64, device=dev)
-        pos0 = torch.zeros(1, dtype=torch.int32, device=dev)
-        logits = m.forward_prefill(tokens, pos0, k_tmp, v_tmp)
-        BS = self.pool.block_size
-        blocks = self.pool.table(sid).blocks
-        for li in range(m.spec.num_layers):
-            for j in range(0, S, BS):
-                blk = blocks[j // BS]
-                n = min(BS, S - j)
-                self.pool.k[li][blk, :, :n, :] = k_tmp[li][0, :, j:j + n, :]
-                self.pool.v[li][blk, :, :n, :] = v_tmp[li][0, :, j:j + n, :]
+        logits = self._prefill_paged(sid, ids, 0)
         first = int(logits[0].argmax())
         sess = Session(sid=sid, prompt_ids=ids, generated=[first], pos=S,
-                       max_new_tokens=max_new_tokens)
+                       max_new_tokens=max_new_tokens, context_ids=list(ids))
         if first == self.eos:
             sess.done = True
         self.sessions[sid] = sess
         return sid
+
+    def _prefill_paged(self, sid: int, ids: List[int],
+                       pos0: int) -> torch.Tensor:
+        """Prefill ``ids`` at rows [pos0, pos0 + len(ids)) of session sid's
+        blocks (already reserved), in slices of LocalEngine.PREFILL_CHUNK;
+        returns the last position's logits [1, vocab]."""
+        m, dev = self.model, self.model.device
+        table = torch.tensor([self.pool.table(sid).blocks],
+                             dtype=torch.int32, device=dev)
+        chunk = self.engine.PREFILL_CHUNK
+        logits = None
+        for j in range(0, len(ids), chunk):
+            tokens = torch.tensor([ids[j:j + chunk]], dtype=torch.int64,
+                                  device=dev)
+            p0 = torch.full((1,), pos0 + j, dtype=torch.int32, device=dev)
+            logits = m.forward_prefill_paged(tokens, p0, self.pool.k,
+                                             self.pool.v, table)
+        return logits
+
+    def extend(self, sid: int, prompt: Union[str, List[int]],
+               max_new_tokens: int = 256) -> int:
+        """Continue a FINISHED session with new prompt tokens (a tool
+        result, the next user message); returns the first token of the new
+        turn (greedy). The conversation so far is not prefilled again.
+
+        The pool holds KV rows for prompt + generated[:-1] and ``pos``
+        counts them: the last emitted token has no row yet. So the prefill
+        is [generated[-1]] + new tokens at pos0 = pos. A turn that ended at
+        an EOS inside a step_chunk left garbage rows past ``pos``; they are
+        never attended: this prefill writes rows pos .. pos + len(new)
+        before it reads them, attention is causal, and every later decode
+        step writes row p before it attends [0, p].
+
+        Raises KeyError (unknown session), ValueError (the session is still
+        active, or pos + 1 + len(new) + max_new_tokens exceeds the model's
+        max_seq_len) and MemoryError (no blocks; the session, its block
+        list and the free list are left exactly as they were)."""
+        s = self.sessions[sid]                      # KeyError: unknown
+        if not s.done:
+            raise ValueError(f"session {sid} is still active")
+        new_ids = (self.engine.tokenizer.encode(prompt)
+                   if isinstance(prompt, str) else list(prompt))
+        n = 1 + len(new_ids)
+        if s.pos + n + max_new_tokens > self.model.max_seq_len:
+            raise ValueError(
+                f"session {sid}: context {s.pos} + {n} new + "
+                f"{max_new_tokens} to generate exceeds max_seq_len "
+                f"{self.model.max_seq_len}")
+        t = self.pool.table(sid)
+        held, length = len(t.blocks), t.length
+        try:
+            self.pool.ensure_capacity(sid, s.pos + n + 1)
+        except MemoryError:
+            self.pool.truncate(sid, held * self.pool.block_size)
+            t.length = length
+            raise
+        logits = self._prefill_paged(sid, [s.generated[-1]] + new_ids, s.pos)
+        first = int(logits[0].argmax())
+        s.context_ids = s.context_ids + self._emitted(s) + new_ids
+        s.pos += n
+        s.generated = [first]
+        s.max_new_tokens = max_new_tokens
+        s.turn += 1
+        s.done = first == self.eos
+        return first
+
+    def _emitted(self, s: Session) -> List[int]:
+        """The current turn's tokens, cut at the first EOS (inclusive)."""
+        gen = s.generated
+        if self.eos in gen:
+            gen = gen[: gen.index(self.eos) + 1]
+        return list(gen)
 
     def close(self, sid: int) -> None:
         self.pool.release(sid)
@@ -257,12 +324,11 @@ class PagedSessionManager:
 
     def result(self, sid: int) -> Dict[str, object]:
         s = self.sessions[sid]
-        gen = s.generated
-        if self.eos in gen:
-            gen = gen[: gen.index(self.eos) + 1]
+        gen = self._emitted(s)
         return {"token_ids": gen,
                 "text": self.engine.tokenizer.decode(gen),
-                "done": s.done}
+                "done": s.done,
+                "turn": s.turn}
 
     # -- model forward over the pool ------------------------------------------
 

@@ -414,18 +414,54 @@ class LlamaModel:
         """Prefill S tokens -> logits of the LAST position [B, vocab]
         (or of every position [B, S, vocab] when ``all_positions`` — the
         ragged-batch path gathers each row's own last real token)."""
+        scale = 1.0 / math.sqrt(self.D)
+
+        def attend(li, q, k, v):
+            ops.rope_kv_prefill(q, k, v, k_caches[li], v_caches[li], pos0, self.rope)
+            return ops.attn_prefill(q, k_caches[li], v_caches[li], pos0, scale=scale)
+
+        return self._prefill_layers(tokens, attend, all_positions)
+
+    def forward_prefill_paged(
+        self,
+        tokens: torch.Tensor,         # [B, S]
+        pos0: torch.Tensor,           # [B] int32 (first absolute position)
+        k_pools: List[torch.Tensor],  # per layer [num_blocks, Hkv, BS, D]
+        v_pools: List[torch.Tensor],
+        block_table: torch.Tensor,    # [B, max_blocks] int32
+        all_positions: bool = False,
+    ) -> torch.Tensor:
+        """forward_prefill over a paged KV pool (engine/kv_cache.PagedKVPool):
+        the same layers with the append and the attention going through the
+        block table (ops.rope_kv_prefill_paged / ops.attn_prefill_paged), so
+        a session prefills straight into its blocks. block_table must map
+        every row below pos0[b] + S. tp = 1 only."""
+        if self.tp_size != 1:
+            raise RuntimeError("forward_prefill_paged is single-GPU (tp=1)")
+        scale = 1.0 / math.sqrt(self.D)
+
+        def attend(li, q, k, v):
+            ops.rope_kv_prefill_paged(q, k, v, k_pools[li], v_pools[li],
+                                      block_table, pos0, self.rope)
+            return ops.attn_prefill_paged(q, k_pools[li], v_pools[li],
+                                          block_table, pos0, scale=scale)
+
+        return self._prefill_layers(tokens, attend, all_positions)
+
+    def _prefill_layers(self, tokens, attend, all_positions):
+        """The prefill layer stack; ``attend(li, q, k, v)`` appends layer
+        li's K/V rows (roping q in place) and returns the attention output
+        [B, S, Hq, D]."""
         s = self.spec
         B, S = tokens.shape
         h = F.embedding(tokens.long(), self.emb)          # [B,S,C] residual
-        scale = 1.0 / math.sqrt(self.D)
         n_layers = len(self.layers)
         x = ops.rmsnorm(h, self.layers[0].norm_attn, s.norm_eps)
         for li, lw in enumerate(self.layers):
             qkv = F.linear(x, lw.wqkv)                    # [B,S,W]
             qkv2 = qkv.view(B * S, -1)
             q, k, v = self._qkv_views(qkv2, B, S)
-            ops.rope_kv_prefill(q, k, v, k_caches[li], v_caches[li], pos0, self.rope)
-            att = ops.attn_prefill(q, k_caches[li], v_caches[li], pos0, scale=scale)
+            att = attend(li, q, k, v)
             o = F.linear(att.reshape(B, S, -1), lw.wo)
             all_reduce_sum(o, self.tp)
             x, h = ops.fused_add_rmsnorm(o, h, lw.norm_mlp, s.norm_eps)

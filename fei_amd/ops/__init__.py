@@ -88,6 +88,14 @@ def _try_load() -> None:
     lib.fei_attn_decode_paged.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i, _i, _i, _i, _i, _i, _i, _f,
                                           _l, _vp, _vp, _vp, _l, _vp]
+    lib.fei_rope_kv_prefill_paged.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _i, _i, _i, _i, _i,
+                                              _i, _i, _l, _l, _vp]
+    lib.fei_rope_kv_prefill_paged.restype = _i
+    lib.fei_attn_prefill_paged.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp,
+                                           _i, _i, _i, _i, _i, _i, _i, _f,
+                                           _l, _vp]
+    lib.fei_attn_prefill_paged.restype = _i
     lib.fei_add_layernorm.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _f,
                                       _i, _vp]
     lib.fei_gelu.argtypes = [_vp, _vp, _l, _vp]
@@ -1092,6 +1100,129 @@ def attn_decode_paged(q, k_pool, v_pool, block_table, pos, splits: int = 32,
                               q.stride(0), kin, vin, cs, kv_bs, _stream())
     lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
                                 B, Hq, D, splits, _stream())
+    return out
+
+
+# -- prefill over a paged KV pool (csrc/attn_prefill_paged.hip) --------------
+
+def _paged_check(name: str, q, k_pool, block_table, pos0) -> Tuple[int, int]:
+    """Shared argument checks of the paged prefill ops; returns (Hkv, BS)."""
+    B, S, Hq, D = q.shape
+    Hkv, BS = k_pool.shape[1], k_pool.shape[2]
+    if Hkv <= 0 or Hq % Hkv != 0:
+        raise ValueError(f"{name}: Hq={Hq} is not a multiple of Hkv={Hkv}")
+    if BS <= 0 or BS & (BS - 1):
+        raise ValueError(f"{name}: block size must be a power of two, "
+                         f"got {BS}")
+    if q.is_cuda and D not in (64, 128):
+        raise ValueError(f"{name} supports D in (64,128), got {D}")
+    if block_table.dim() != 2 or block_table.shape[0] != B or \
+            block_table.dtype != torch.int32:
+        raise ValueError(f"{name}: block_table must be int32 [B, max_blocks]")
+    if not pos0.is_cuda and B > 0 and \
+            block_table.shape[1] * BS < int(pos0.max()) + S:
+        raise ValueError(
+            f"{name}: block_table covers {block_table.shape[1] * BS} rows, "
+            f"the prefill reaches row {int(pos0.max()) + S}")
+    return Hkv, BS
+
+
+def _gather_pool(pool: torch.Tensor, block_table: torch.Tensor,
+                 n_rows) -> torch.Tensor:
+    """Contiguous [B, Hkv, max(n_rows), D] copy of the first n_rows[b] logical
+    rows of every sequence (reference path). Table entries past a sequence's
+    last needed block are never looked at (production tables hold -1)."""
+    _, Hkv, BS, D = pool.shape
+    B = block_table.shape[0]
+    out = pool.new_zeros(B, Hkv, max(max(n_rows), 1), D)
+    for b in range(B):
+        for j in range(0, n_rows[b], BS):
+            n = min(BS, n_rows[b] - j)
+            out[b, :, j:j + n] = pool[int(block_table[b, j // BS]), :, :n]
+    return out
+
+
+def rope_kv_prefill_paged(q, k, v, k_pool, v_pool, block_table, pos0,
+                          table) -> torch.Tensor:
+    """rope_kv_prefill into a PAGED pool: in-place RoPE on q [B,S,Hq,D]; k
+    roped + v appended at logical row pos0[b]+s, i.e. pool[block_table[b,
+    p >> log2(BS)], :, p & (BS-1), :]. Pools [num_blocks, Hkv, BS, D], BS a
+    power of two; block_table [B, max_blocks] int32. Same arithmetic as
+    rope_kv_prefill: the rows are bit-equal to the contiguous cache's.
+
+    Contract on GPU (not checked: it would cost a host sync): block_table
+    holds a valid block for every row below max(pos0) + S."""
+    Hkv, BS = _paged_check("rope_kv_prefill_paged", q, k_pool, block_table,
+                           pos0)
+    B, S, Hq, D = q.shape
+    if not q.is_cuda:
+        n = int(pos0.max()) + S if B > 0 else 0
+        kc = k_pool.new_zeros(B, Hkv, max(n, 1), D)
+        vc = torch.zeros_like(kc)
+        q_out = ref.rope_kv_prefill(q, k, v, kc, vc, pos0, table)
+        bs_log = BS.bit_length() - 1
+        for b in range(B):
+            for p in range(int(pos0[b]), int(pos0[b]) + S):
+                blk = int(block_table[b, p >> bs_log])
+                k_pool[blk, :, p & (BS - 1)] = kc[b, :, p]
+                v_pool[blk, :, p & (BS - 1)] = vc[b, :, p]
+        q.copy_(q_out)
+        return q
+    lib = require_lib()
+    assert q.stride(3) == 1 and q.stride(2) == D
+    assert q.stride(0) == S * q.stride(1), "token rows must be uniform"
+    assert k.stride(2) == D and k.stride(0) == S * k.stride(1)
+    assert k.stride(1) == v.stride(1)
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    assert block_table.is_contiguous()
+    rc = lib.fei_rope_kv_prefill_paged(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(k_pool), _ptr(v_pool),
+        _ptr(block_table), _ptr(table), _ptr(pos0), B, S, Hq, Hkv, D, BS,
+        block_table.shape[1], q.stride(1), k.stride(1), _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_rope_kv_prefill_paged refused the launch (rc={rc})")
+    return q
+
+
+def attn_prefill_paged(q, k_pool, v_pool, block_table, pos0,
+                       scale: Optional[float] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal GQA attention of q [B,S,Hq,D] (roped) over a PAGED pool: q
+    token s attends the logical rows [0, pos0[b]+s] of sequence b. Pools
+    [num_blocks, Hkv, BS, D], BS a power of two; block_table [B, max_blocks]
+    int32. Bit-equal to attn_prefill over the gathered rows. Table entries
+    of blocks no row below pos0[b]+S lives in are never read (-1 is fine).
+
+    Contract on GPU (not checked: it would cost a host sync): block_table
+    holds a valid block for every row below max(pos0) + S."""
+    Hkv, BS = _paged_check("attn_prefill_paged", q, k_pool, block_table, pos0)
+    B, S, Hq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if not q.is_cuda:
+        n_rows = [int(pos0[b]) + S for b in range(B)]
+        kc = _gather_pool(k_pool, block_table, n_rows)
+        vc = _gather_pool(v_pool, block_table, n_rows)
+        res = ref.attn_prefill(q, kc, vc, pos0, scale)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    lib = require_lib()
+    if out is None:
+        out = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+    assert q.stride(3) == 1 and q.stride(2) == D
+    assert q.stride(0) == S * q.stride(1)
+    assert out.is_contiguous()
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    assert block_table.is_contiguous()
+    rc = lib.fei_attn_prefill_paged(
+        _ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(block_table), _ptr(out),
+        _ptr(pos0), B, S, Hq, Hkv, D, BS, block_table.shape[1], scale,
+        q.stride(1), _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_attn_prefill_paged refused the launch (rc={rc})")
     return out
 
 

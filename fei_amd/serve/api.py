@@ -7,6 +7,7 @@ POST /v1/chat/completions   messages=[{role, content}], ... (+ stream SSE)
 POST /v1/sessions           open a paged continuous-batching session
 POST /v1/sessions/step      advance all sessions (?n=K)
 GET  /v1/sessions/{id}      poll result     DELETE /v1/sessions/{id}  close
+POST /v1/sessions/{id}/extend   continue a finished session (next turn)
 GET  /v1/models             available ModelSpecs
 GET  /health                engine + device status
 
@@ -52,6 +53,11 @@ class ChatMessage(BaseModel):
 
 
 class SessionOpen(BaseModel):
+    prompt: str
+    max_tokens: int = 256
+
+
+class SessionExtend(BaseModel):
     prompt: str
     max_tokens: int = 256
 
@@ -294,6 +300,28 @@ def create_app(engine: Optional[LocalEngine] = None,
         if sid not in mgr.sessions:
             raise HTTPException(status_code=404, detail="no such session")
         return {"session_id": sid, **mgr.result(sid)}
+
+    @app.post("/v1/sessions/{sid}/extend")
+    def session_extend(sid: int, req: SessionExtend):
+        """Continue a finished session with new prompt tokens (the next
+        turn): 404 unknown session, 409 still decoding, 400 context
+        overflow, 503 pool exhausted (the session is left untouched)."""
+        from fastapi import HTTPException
+        with lock:
+            mgr = _mgr()
+            if sid not in mgr.sessions:
+                raise HTTPException(status_code=404, detail="no such session")
+            if not mgr.sessions[sid].done:
+                raise HTTPException(status_code=409,
+                                    detail="session is still active")
+            try:
+                first = mgr.extend(sid, req.prompt,
+                                   max_new_tokens=req.max_tokens)
+            except ValueError as e:          # context overflow
+                raise HTTPException(status_code=400, detail=str(e))
+            except MemoryError as e:
+                raise HTTPException(status_code=503, detail=str(e))
+        return {"session_id": sid, "first_token": first}
 
     @app.delete("/v1/sessions/{sid}")
     def session_close(sid: int):
