@@ -252,13 +252,16 @@ class LlamaModel:
                              device=h.device)
             nbuf = 0
         d = None
+        # sharded GEMVs keep k_gemv: the deep kernel's dispatch rule was
+        # measured on one GPU only (profiles/gemv_deep.md)
+        deep = None if self.tp_size == 1 else False
         for li, lw in enumerate(self.layers):
             if addnorm and li > 0:
                 qkv = ops.gemv_addnorm(d, h, hb[nbuf], lw.norm_attn, lw.wqkv,
                                        s.norm_eps)
                 h, nbuf = hb[nbuf], nbuf ^ 1
             else:
-                qkv = ops.linear_decode(x, lw.wqkv)
+                qkv = ops.linear_decode(x, lw.wqkv, deep=deep)
             q, k, v = self._qkv_views(qkv, B)
             if fused_attn:
                 att = ops.attn_decode_fused(q, k, v, k_caches[li],
@@ -270,7 +273,7 @@ class LlamaModel:
                                       splits=attn_splits, scale=scale,
                                       workspace=workspace, out=attn_out,
                                       k=k, v=v, table=self.rope, layer=li)
-            o = ops.linear_decode(att.reshape(B, -1), lw.wo)
+            o = ops.linear_decode(att.reshape(B, -1), lw.wo, deep=deep)
             all_reduce_sum(o, self.tp)
             if addnorm:
                 act = ops.gemv_swiglu_addnorm(o, h, hb[nbuf], lw.norm_mlp,
@@ -279,14 +282,14 @@ class LlamaModel:
             else:
                 x, h = ops.fused_add_rmsnorm(o, h, lw.norm_mlp, s.norm_eps)
                 act = ops.gemv_swiglu(x, lw.wgu)
-            d = ops.linear_decode(act, lw.wdown)
+            d = ops.linear_decode(act, lw.wdown, deep=deep)
             all_reduce_sum(d, self.tp)
             if addnorm and li + 1 < n_layers:
                 continue                  # folded into the next layer's qkv
             next_norm = (self.layers[li + 1].norm_attn if li + 1 < n_layers
                          else self.norm_f)
             x, h = ops.fused_add_rmsnorm(d, h, next_norm, s.norm_eps)
-        logits = ops.linear_decode(x, self.lm_head)
+        logits = ops.linear_decode(x, self.lm_head, deep=deep)
         if gather_logits:
             logits = all_gather_cat(logits, dim=-1, ctx=self.tp)
         return logits

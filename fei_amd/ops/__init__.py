@@ -116,6 +116,8 @@ def _try_load() -> None:
         fn.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i,
                        _vp]
         fn.restype = _i
+    lib.fei_gemv_deep.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
+    lib.fei_gemv_deep.restype = _i
     _LIB = lib
 
 
@@ -779,6 +781,17 @@ _FUSED_CMB = os.environ.get("FEI_FUSED_CMB", "0") == "1"
 # restores the launches for A/B inside one build
 # (profiles/gemv_addnorm.md).
 _ADDNORM_GEMV = os.environ.get("FEI_ADDNORM_GEMV", "1") == "1"
+# Batch-1 GEMVs whose grid is too small to hide HBM latency with occupancy
+# (o and down at N = 4096: 2 workgroups per CU) run the deep-pipelined
+# k_gemv_deep, bit-identical to k_gemv. The gate is workgroups per CU, not a
+# shape: below _GEMV_DEEP_MAX_WG_PER_CU the plain kernel cannot fill a CU's
+# 8 resident workgroups. FEI_GEMV_DEEP=0 restores k_gemv everywhere for A/B
+# inside one build (profiles/gemv_deep.md).
+_GEMV_DEEP = os.environ.get("FEI_GEMV_DEEP", "1") == "1"
+_GEMV_DEEP_MAX_WG_PER_CU = float(
+    os.environ.get("FEI_GEMV_DEEP_MAX_WG_PER_CU", "8") or 8)
+_GEMV_DEEP_MAX_TRIPS = 8           # trips of 4096 columns, as in gemv.hip
+_CU_COUNT: dict = {}
 
 
 def _gemm_m8_ok(M: int, N: int, K: int) -> bool:
@@ -792,11 +805,37 @@ def _gemv_ok(M: int, K: int) -> bool:
     return M in (1, 2, 4, 8) and K % 8 == 0
 
 
+def _cu_count(device: torch.device) -> int:
+    idx = device.index if device.index is not None else \
+        torch.cuda.current_device()
+    if idx not in _CU_COUNT:
+        _CU_COUNT[idx] = torch.cuda.get_device_properties(
+            idx).multi_processor_count
+    return _CU_COUNT[idx]
+
+
+def _gemv_deep_ok(M: int, K: int) -> bool:
+    return (M == 1 and K > 0 and K % 8 == 0
+            and -(-K // 4096) <= _GEMV_DEEP_MAX_TRIPS)
+
+
+def _gemv_deep_wins(N: int, K: int, device: torch.device) -> bool:
+    """The dispatch rule: k_gemv's grid ((N + 7) // 8 workgroups) leaves the
+    CUs short of resident waves."""
+    return (_GEMV_DEEP and _gemv_deep_ok(1, K)
+            and (N + 7) // 8 < _GEMV_DEEP_MAX_WG_PER_CU * _cu_count(device))
+
+
 def linear_decode(x: torch.Tensor, w: torch.Tensor,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None,
+                  deep: Optional[bool] = None) -> torch.Tensor:
     """F.linear for skinny M: hand-rolled streaming GEMV on GPU
     (profiles/r01: rocBLAS reaches ~4 TB/s on M=1; streaming reaches the
-    flat-read ceiling). Falls back to torch for unsupported shapes/CPU."""
+    flat-read ceiling). Falls back to torch for unsupported shapes/CPU.
+
+    ``deep`` picks the batch-1 kernel: True the deep-pipelined k_gemv_deep
+    (an error where it does not apply), False k_gemv, None the dispatch rule
+    (_gemv_deep_wins). Both give the same bits."""
     M = x.numel() // x.shape[-1]
     K = x.shape[-1]
     N = w.shape[0]
@@ -814,6 +853,15 @@ def linear_decode(x: torch.Tensor, w: torch.Tensor,
         # fetch measured 6.50 vs 5.01 ms/step at batch 8.
         lib.fei_gemm_m8(_ptr(out), _ptr(x2), _ptr(w), M, N, K, 0,
                         _stream())
+        return out
+    if deep is None:
+        deep = M == 1 and _gemv_deep_wins(N, K, x.device)
+    if deep:
+        rc = lib.fei_gemv_deep(_ptr(out), _ptr(x2), _ptr(w), M, N, K, nt,
+                               _stream())
+        if rc != 0:
+            raise ValueError(
+                f"gemv_deep does not take M={M} N={N} K={K} (code {rc})")
         return out
     lib.fei_gemv(_ptr(out), _ptr(x2), _ptr(w), M, N, K, nt, _stream())
     return out

@@ -149,6 +149,152 @@ void fei_gemv_swiglu(void* out, const void* x, const void* w, int M, int N,
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
+// Deep-pipelined batch-1 GEMV for grids too small to hide HBM latency with
+// occupancy (o and down at N = 4096: 512 workgroups, 2 waves per SIMD).
+// k_gemv's loop is not unrolled by hipcc and waits vmcnt(0) every iteration:
+// 2 KB of weights in flight per wave, one memory round trip per 512 columns.
+// Here a wave keeps a ring of D loop iterations (x and both weight rows) in
+// registers: all D are issued before the first dot, and slot u is refilled
+// with iteration i + D right after iteration i has been dotted out of it, so
+// D - 1 iterations (2 (D - 1) weight loads) stay in flight behind every wait.
+// At K = 4096 and D = 8 that is the whole row slice at once.
+//
+// The T trips round the ring are a template parameter, T = ceil(K / (512 D)),
+// and the kernel is straight-line code: as a runtime loop the ring's
+// registers become loop-carried values that hipcc copies and parks in AGPRs
+// (285 registers, a wait for 20 of the first 24 loads before the first dot);
+// unrolled it is 128 VGPRs with vmcnt(21..26) at every wait.
+//
+// Same grid, row-to-wave and lane-to-column mapping as k_gemv, and the same
+// per-lane chain acc += dot8_bf16(x_i, w_i) over ascending i from +0.f, so
+// the output is bit-identical. Indices past the row clamp to its last vec8
+// (an in-bounds duplicate) and the guard is a select on the accumulator: a
+// branch lets hipcc sink the loads behind it with a vmcnt(0)
+// (profiles/gemv_addnorm.md). x goes out ahead of the weights of the same
+// slot because the memory counter retires in issue order.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+template <bool NT>
+__device__ __forceinline__ s16x8 ldw_deep(const s16x8* p) {
+  return NT ? __builtin_nontemporal_load(p) : *p;
+}
+
+// One trip round the ring: dot iterations base + u*64 + lane, u = 0..D-1, in
+// ascending order. REFILL: slot u is reloaded for the next trip.
+template <int D, bool NT, bool REFILL>
+__device__ __forceinline__ void deep_ring(float& acc0, float& acc1,
+                                          s16x8 (&xv)[D], s16x8 (&wv0)[D],
+                                          s16x8 (&wv1)[D],
+                                          const s16x8* __restrict__ xr,
+                                          const s16x8* __restrict__ wrow0,
+                                          const s16x8* __restrict__ wrow1,
+                                          int base, int nv, int lane) {
+#pragma unroll
+  for (int u = 0; u < D; ++u) {
+    const int i = base + u * 64 + lane;
+    const float d0 = dot8_bf16(xv[u], wv0[u]);
+    const float d1 = dot8_bf16(xv[u], wv1[u]);
+    acc0 = i < nv ? acc0 + d0 : acc0;       // select, not a branch per load
+    acc1 = i < nv ? acc1 + d1 : acc1;
+    if (REFILL) {
+      const int j = min(i + D * 64, nv - 1);
+      xv[u] = xr[j];
+      wv0[u] = ldw_deep<NT>(&wrow0[j]);
+      wv1[u] = ldw_deep<NT>(&wrow1[j]);
+    }
+    // one slot at a time: keeps the refill right behind its dot and stops
+    // the scheduler widening every slot to f32 up front
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <int D, bool NT, int T>
+__global__ void __launch_bounds__(256)
+k_gemv_deep(u16* __restrict__ out, const u16* __restrict__ x,
+            const u16* __restrict__ w, int N, int K) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int n0 = blockIdx.x * 8 + wid * 2;
+  if (n0 >= N) return;
+  const bool two = (n0 + 1) < N;
+  const s16x8* xr = (const s16x8*)x;
+  const s16x8* wrow0 = (const s16x8*)(w + (long)n0 * K);
+  const s16x8* wrow1 = (const s16x8*)(w + (long)(n0 + (two ? 1 : 0)) * K);
+  const int nv = K >> 3;                      // vec8 per row, >= 1
+
+  s16x8 xv[D], wv0[D], wv1[D];
+#pragma unroll
+  for (int u = 0; u < D; ++u) xv[u] = xr[min(lane + u * 64, nv - 1)];
+#pragma unroll
+  for (int u = 0; u < D; ++u) {
+    const int j = min(lane + u * 64, nv - 1);
+    wv0[u] = ldw_deep<NT>(&wrow0[j]);
+    wv1[u] = ldw_deep<NT>(&wrow1[j]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
+  float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+  for (int t = 0; t < T - 1; ++t)
+    deep_ring<D, NT, true>(acc0, acc1, xv, wv0, wv1, xr, wrow0, wrow1,
+                           t * D * 64, nv, lane);
+  deep_ring<D, NT, false>(acc0, acc1, xv, wv0, wv1, xr, wrow0, wrow1,
+                          (T - 1) * D * 64, nv, lane);
+
+  const float v0 = wave_reduce_sum(acc0);
+  const float v1 = wave_reduce_sum(acc1);
+  if (lane == 0) {
+    out[n0] = f2bf(v0);
+    if (two) out[n0 + 1] = f2bf(v1);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// out[1, N] = x[1, K] @ W[N, K]^T, bit-identical to fei_gemv at M = 1.
+// Returns 0, or a negative code with nothing launched: -1 for a batch other
+// than 1, -2 for N < 1 or a K that is not a positive multiple of 8 or needs
+// more than FEI_GEMV_DEEP_MAX_TRIPS trips round the ring.
+#define FEI_GEMV_DEEP_RING 8
+#define FEI_GEMV_DEEP_MAX_TRIPS 8
+int fei_gemv_deep(void* out, const void* x, const void* w, int M, int N,
+                  int K, int nontemporal, hipStream_t stream) {
+  if (M != 1) return -1;
+  if (K <= 0 || K % 8 != 0 || N < 1) return -2;
+  const int per_trip = FEI_GEMV_DEEP_RING * 64;
+  const int trips = ((K >> 3) + per_trip - 1) / per_trip;
+  if (trips > FEI_GEMV_DEEP_MAX_TRIPS) return -2;
+  dim3 grid((N + 7) / 8);
+#define LD(TV) do { \
+    if (nontemporal) \
+      hipLaunchKernelGGL((k_gemv_deep<FEI_GEMV_DEEP_RING, true, TV>), grid, \
+          dim3(256), 0, stream, (u16*)out, (const u16*)x, (const u16*)w, N, K); \
+    else \
+      hipLaunchKernelGGL((k_gemv_deep<FEI_GEMV_DEEP_RING, false, TV>), grid, \
+          dim3(256), 0, stream, (u16*)out, (const u16*)x, (const u16*)w, N, K); \
+  } while (0)
+  switch (trips) {
+    case 1: LD(1); break;
+    case 2: LD(2); break;
+    case 3: LD(3); break;
+    case 4: LD(4); break;
+    case 5: LD(5); break;
+    case 6: LD(6); break;
+    case 7: LD(7); break;
+    default: LD(8); break;
+  }
+#undef LD
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
 // Fused-chain GEMV variants (tp=1 decode): the residual stream never leaves
 // the GEMV kernels —
 //   k_gemv_res:  res[m,n] += x[m,:] @ W[n,:]      (epilogue residual add)
