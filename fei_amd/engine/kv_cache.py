@@ -11,6 +11,14 @@ k_rope_kv_prefill_paged and k_attn_prefill_paged (prefill and multi-turn
 continuation). The allocator is host-side bookkeeping only: blocks are
 handed out, grown (ensure_capacity), given back (truncate, release) and
 copied (fork); it never moves a row.
+
+``kv_quant="fp8"`` stores the rows in the fp8 format of
+reference.quant_kv_fp8: every layer is an ops.QuantKV (e4m3fn codes
+[num_blocks, Hkv, BS, D] + one f32 scale per row [num_blocks, Hkv, BS]) and
+the kernels are their fp8 forms in csrc/kv_fp8_paged.hip
+(k_attn_decode_paged_kv8, k_rope_kv8_prefill_paged,
+k_attn_prefill_paged_kv8). A row costs D + 4 bytes instead of 2*D, so the
+same memory budget holds 2*D / (D + 4) times the blocks (1.94x at D = 128).
 """
 
 from __future__ import annotations
@@ -20,6 +28,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from fei_amd import ops
 from fei_amd.utils.logging import get_logger
 
 logger = get_logger("engine.kv_cache")
@@ -37,7 +46,9 @@ class PagedKVPool:
     """Fixed-size block pool over one big tensor pair per layer.
 
     layout per layer: [num_blocks, Hkv, block_size, D] — a sequence's
-    logical block i lives at physical index table.blocks[i].
+    logical block i lives at physical index table.blocks[i]. With
+    ``kv_quant="fp8"`` a layer is an ops.QuantKV of that shape (codes) plus
+    [num_blocks, Hkv, block_size] f32 scales; ``dtype`` is then unused.
     """
 
     def __init__(
@@ -50,7 +61,12 @@ class PagedKVPool:
         device: Optional[torch.device] = None,
         dtype: torch.dtype = torch.bfloat16,
         mem_fraction: float = 0.6,
+        kv_quant: Optional[str] = None,
     ):
+        if kv_quant not in (None, "fp8"):
+            raise ValueError(
+                f"kv_quant must be None or 'fp8', got {kv_quant!r}")
+        self.kv_quant = kv_quant
         self.block_size = block_size
         self.device = device or (torch.device("cuda:0") if torch.cuda.is_available()
                                  else torch.device("cpu"))
@@ -61,18 +77,34 @@ class PagedKVPool:
                 budget = int(free * mem_fraction)
             else:
                 budget = 1 << 28
+            # bytes of one row: D elements, or D codes + one f32 scale
+            row_bytes = (head_dim + 4 if kv_quant == "fp8" else
+                         head_dim * torch.tensor([], dtype=dtype).element_size())
             bytes_per_block = (2 * num_layers * num_kv_heads * block_size *
-                               head_dim * torch.tensor([], dtype=dtype).element_size())
+                               row_bytes)
             num_blocks = max(16, budget // bytes_per_block)
         self.num_blocks = int(num_blocks)
         shape = (self.num_blocks, num_kv_heads, block_size, head_dim)
-        self.k = [torch.zeros(shape, device=self.device, dtype=dtype)
-                  for _ in range(num_layers)]
-        self.v = [torch.zeros(shape, device=self.device, dtype=dtype)
-                  for _ in range(num_layers)]
+        if kv_quant == "fp8":
+            self.k = [ops.QuantKV.zeros(shape, self.device)
+                      for _ in range(num_layers)]
+            self.v = [ops.QuantKV.zeros(shape, self.device)
+                      for _ in range(num_layers)]
+        else:
+            self.k = [torch.zeros(shape, device=self.device, dtype=dtype)
+                      for _ in range(num_layers)]
+            self.v = [torch.zeros(shape, device=self.device, dtype=dtype)
+                      for _ in range(num_layers)]
         self._free: List[int] = list(range(self.num_blocks - 1, -1, -1))
         self._tables: Dict[int, BlockTable] = {}
         self._next_id = 0
+
+    @property
+    def kv_dtype(self) -> str:
+        """Element format of the pool's rows: "fp8", "bf16" or "fp32"."""
+        if self.kv_quant == "fp8":
+            return "fp8"
+        return "bf16" if self.dtype == torch.bfloat16 else "fp32"
 
     # -- sessions ------------------------------------------------------------
 
@@ -128,7 +160,8 @@ class PagedKVPool:
 
     def fork(self, seq_id: int) -> int:
         """Copy-on-write-free fork is not supported (blocks are mutable);
-        makes a physical copy of the parent's blocks."""
+        makes a physical copy of the parent's blocks (codes and scales in
+        an fp8 pool)."""
         parent = self._tables[seq_id]
         child_id = self.new_sequence()
         child = self._tables[child_id]
@@ -136,9 +169,11 @@ class PagedKVPool:
             if not self._free:
                 raise MemoryError("KV pool exhausted during fork")
             nb = self._free.pop()
-            for lk, lv in zip(self.k, self.v):
-                lk[nb].copy_(lk[pb])
-                lv[nb].copy_(lv[pb])
+            for layer in self.k + self.v:
+                parts = ((layer.data, layer.scale)
+                         if isinstance(layer, ops.QuantKV) else (layer,))
+                for t in parts:
+                    t[nb].copy_(t[pb])
             child.blocks.append(nb)
         child.length = parent.length
         return child_id

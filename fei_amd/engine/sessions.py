@@ -13,6 +13,13 @@ Prompts are prefilled straight into the session's blocks
 prompt tokens (`extend`: a tool result, the next user message) without
 re-prefilling the conversation: open -> step -> result -> extend -> step ...
 
+The pool follows the engine's KV format: on an engine built with
+``kv_quant="fp8"`` (or with an explicit ``kv_quant="fp8"`` here) the sessions
+live in fp8 blocks (e4m3fn codes + one f32 scale per row, ops.QuantKV pool
+layers) and every read and write goes through the fp8 paged kernels
+(csrc/kv_fp8_paged.hip) — 2*D / (D + 4) times the blocks for the same
+``mem_fraction``.
+
 Control-plane costs stay host-side (per-step RoPE/append scatter is a few
 microseconds of torch indexing per layer); the O(context) work — attention
 over the pool — is the paged HIP kernel, and all GEMVs take the same
@@ -56,16 +63,24 @@ class Session:
 class PagedSessionManager:
     def __init__(self, engine, block_size: int = 16,
                  num_blocks: Optional[int] = None,
-                 mem_fraction: float = 0.25):
+                 mem_fraction: float = 0.25,
+                 kv_quant: Optional[str] = None):
+        """``kv_quant``: None inherits ``engine.kv_quant``; "fp8" asks for an
+        fp8 pool; "none" for an unquantised pool whatever the engine uses."""
         self.engine = engine
         self.model = engine.model
         m = self.model
         assert m.tp_size == 1, "paged session serving is single-GPU"
 
+        if kv_quant is None:
+            kv_quant = getattr(engine, "kv_quant", None)
+        elif kv_quant == "none":
+            kv_quant = None
         self.pool = PagedKVPool(
             num_layers=m.spec.num_layers, num_kv_heads=m.hkv_l,
             head_dim=m.D, block_size=block_size, num_blocks=num_blocks,
-            device=m.device, dtype=m.dtype, mem_fraction=mem_fraction)
+            device=m.device, dtype=m.dtype, mem_fraction=mem_fraction,
+            kv_quant=kv_quant)
         self.sessions: Dict[int, Session] = {}
         self.eos = engine.tokenizer.eos_id
         self._ws: Dict[int, tuple] = {}     # split-K workspace per batch size
@@ -82,8 +97,11 @@ class PagedSessionManager:
         # batch-aware split count (engine ctor note): the B-wide grid
         # already fills the chip at 16 splits once B >= 4 — 32 over-splits
         # (batch-8 plain path measured 6.34 -> 5.85 ms/step at 16)
-        return min(self.engine.attn_splits, 16) if B >= 4 \
+        sp = min(self.engine.attn_splits, 16) if B >= 4 \
             else self.engine.attn_splits
+        if self.pool.kv_quant == "fp8":
+            sp = min(sp, self.model.D // 2)     # the fp8 kernel's own limit
+        return sp
 
     def _workspace(self, B: int):
         if B not in self._ws:
@@ -103,7 +121,9 @@ class PagedSessionManager:
         real steps whose KV rows are garbage; they are rewritten by the
         first replays before anything attends them (the per-layer append
         at `pos` precedes the attention read of key `pos`, and rows past
-        the accepted stream are never attended)."""
+        the accepted stream are never attended). In an fp8 pool the same
+        holds for a row's scale as for its codes: the append writes both
+        before the row is read."""
         W = 16
         while W < max_blocks:
             W *= 2
@@ -351,7 +371,9 @@ class PagedSessionManager:
         x = ops.rmsnorm(h, m.layers[0].norm_attn, s.norm_eps)
         pos_l = pos.long()
         gpu = m.device.type == "cuda"
-        if not gpu:
+        # an fp8 pool is never written from here: the op quantises the row
+        fused = gpu or self.pool.kv_quant == "fp8"
+        if not fused:
             blk = table.gather(1, (pos_l // BS).unsqueeze(1)) \
                 .squeeze(1).long()
             off = pos_l % BS
@@ -359,7 +381,7 @@ class PagedSessionManager:
             qkv = ops.linear_decode(x, lw.wqkv)
             q, k, v = m._qkv_views(qkv, B)
             kp, vp = self.pool.k[li], self.pool.v[li]
-            if gpu:
+            if fused:
                 # fused in-kernel RoPE + paged append (the eager torch
                 # rope/append chain was ~15 launches/layer — ~30% of the
                 # serving step)

@@ -429,8 +429,8 @@ class LlamaModel:
         self,
         tokens: torch.Tensor,         # [B, S]
         pos0: torch.Tensor,           # [B] int32 (first absolute position)
-        k_pools: List[torch.Tensor],  # per layer [num_blocks, Hkv, BS, D]
-        v_pools: List[torch.Tensor],
+        k_pools: List,                # per layer [num_blocks, Hkv, BS, D]:
+        v_pools: List,                # tensors, or ops.QuantKV (fp8 pool)
         block_table: torch.Tensor,    # [B, max_blocks] int32
         all_positions: bool = False,
     ) -> torch.Tensor:
@@ -438,7 +438,9 @@ class LlamaModel:
         the same layers with the append and the attention going through the
         block table (ops.rope_kv_prefill_paged / ops.attn_prefill_paged), so
         a session prefills straight into its blocks. block_table must map
-        every row below pos0[b] + S. tp = 1 only."""
+        every row below pos0[b] + S. The ops dispatch on the pool type: an
+        fp8 pool (PagedKVPool(kv_quant="fp8")) takes the fp8 kernels.
+        tp = 1 only."""
         if self.tp_size != 1:
             raise RuntimeError("forward_prefill_paged is single-GPU (tp=1)")
         scale = 1.0 / math.sqrt(self.D)

@@ -96,6 +96,18 @@ def _try_load() -> None:
                                            _i, _i, _i, _i, _i, _i, _i, _f,
                                            _l, _vp]
     lib.fei_attn_prefill_paged.restype = _i
+    lib.fei_rope_kv8_prefill_paged.argtypes = [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+        _i, _i, _i, _i, _i, _i, _i, _l, _l, _vp]
+    lib.fei_rope_kv8_prefill_paged.restype = _i
+    lib.fei_attn_decode_paged_kv8.argtypes = [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+        _i, _i, _i, _i, _i, _i, _i, _f, _l, _vp, _vp, _vp, _l, _vp]
+    lib.fei_attn_decode_paged_kv8.restype = _i
+    lib.fei_attn_prefill_paged_kv8.argtypes = [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+        _i, _i, _i, _i, _i, _i, _i, _f, _l, _vp]
+    lib.fei_attn_prefill_paged_kv8.restype = _i
     lib.fei_add_layernorm.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _f,
                                       _i, _vp]
     lib.fei_gelu.argtypes = [_vp, _vp, _l, _vp]
@@ -1094,7 +1106,14 @@ def attn_decode_paged(q, k_pool, v_pool, block_table, pos, splits: int = 32,
     logical key blocks to physical pool blocks. n = pos[b]+1 keys.
     When (k, v, table) are given the kernel also fuses the step's RoPE +
     paged KV-append: q is the RAW qkv view and the pool row for position
-    pos[b] is written in-kernel (mirrors attn_decode's fused form)."""
+    pos[b] is written in-kernel (mirrors attn_decode's fused form).
+    QuantKV pools (data [num_blocks, Hkv, BS, D], scale [num_blocks, Hkv,
+    BS]) run the fp8 kernel (kv_fp8_paged.hip): bit-equal to attn_decode
+    over a contiguous QuantKV holding the same rows."""
+    if _kv8_pair(k_pool, v_pool):
+        return _attn_decode_paged_kv8(q, k_pool, v_pool, block_table, pos,
+                                      splits, scale, workspace, out, k, v,
+                                      table)
     B, Hq, D = q.shape
     n_blocks, Hkv, BS, _ = k_pool.shape
     assert BS & (BS - 1) == 0, "block size must be a power of two"
@@ -1190,6 +1209,93 @@ def _gather_pool(pool: torch.Tensor, block_table: torch.Tensor,
     return out
 
 
+def _gather_pool_kv8(pool: QuantKV, block_table: torch.Tensor,
+                     n_rows) -> torch.Tensor:
+    """_gather_pool of an fp8 pool, dequantised: f32 [B, Hkv, max(n_rows), D]
+    (reference path; rows past n_rows[b] are zero)."""
+    data = _gather_pool(pool.data, block_table, n_rows)
+    scale = _gather_pool(pool.scale.unsqueeze(-1), block_table,
+                         n_rows).squeeze(-1)
+    return ref.dequant_kv_fp8(data, scale)
+
+
+def _scatter_pool_kv8(pool: QuantKV, block_table: torch.Tensor, b: int,
+                      p: int, codes: torch.Tensor, scales: torch.Tensor):
+    """Write one logical row (codes [Hkv, D], scales [Hkv]) of sequence b
+    through the table (reference path)."""
+    BS = pool.shape[2]
+    blk = int(block_table[b, p // BS])
+    pool.data[blk, :, p % BS, :] = codes
+    pool.scale[blk, :, p % BS] = scales
+
+
+def _attn_decode_paged_kv8(q, k_pool, v_pool, block_table, pos, splits, scale,
+                           workspace, out, k, v, table) -> torch.Tensor:
+    B, Hq, D = q.shape
+    _, Hkv, BS, _ = k_pool.shape
+    name = "attn_decode_paged (fp8)"
+    if BS <= 0 or BS & (BS - 1):
+        raise ValueError(f"{name}: block size must be a power of two, "
+                         f"got {BS}")
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if not q.is_cuda:
+        if table is not None:
+            # the contiguous reference append (ref.rope_kv_decode_fp8): K
+            # roped and rounded to k.dtype, then quantised per row
+            q = ref.apply_rope(q, pos.long(), table)
+            kq, ks = ref.quant_kv_fp8(ref.apply_rope(k, pos.long(), table))
+            vq, vs = ref.quant_kv_fp8(v)
+            for b in range(B):
+                p = int(pos[b])
+                _scatter_pool_kv8(k_pool, block_table, b, p, kq[b], ks[b])
+                _scatter_pool_kv8(v_pool, block_table, b, p, vq[b], vs[b])
+        n_rows = [int(pos[b]) + 1 for b in range(B)]
+        return ref.attn_decode(q, _gather_pool_kv8(k_pool, block_table, n_rows),
+                               _gather_pool_kv8(v_pool, block_table, n_rows),
+                               pos + 1, scale)
+    lib = require_lib()
+    _check_gqa(name, Hq, Hkv)
+    if D not in (64, 128):
+        raise ValueError(f"{name} supports D in (64,128), got {D}")
+    # the combine kernel stages its 2*splits m/l values with D threads
+    if splits <= 0 or 2 * splits > D:
+        raise ValueError(f"{name} needs 0 < 2*splits <= D (splits={splits}, "
+                         f"D={D})")
+    if block_table.dim() != 2 or block_table.shape[0] != B or \
+            block_table.dtype != torch.int32 or \
+            not block_table.is_contiguous():
+        raise ValueError(f"{name}: block_table must be a contiguous int32 "
+                         "[B, max_blocks]")
+    if workspace is None:
+        part_o = torch.empty(B, Hq, splits, D, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(B, Hq, splits, 2, dtype=torch.float32, device=q.device)
+    else:
+        part_o, part_ml = workspace[0], workspace[1]
+        assert part_o.shape[2] == splits and part_ml.shape[2] == splits, \
+            f"workspace sized for {part_o.shape[2]} splits, kernel asked {splits}"
+    if out is None:
+        out = torch.empty_like(q)
+    assert q.stride(2) == 1 and q.stride(1) == D
+    if table is not None:
+        assert k is not None and v is not None
+        assert k.stride(1) == D and k.stride(0) == v.stride(0)
+        kin, vin, cs, kv_bs = _ptr(k), _ptr(v), _ptr(table), k.stride(0)
+    else:
+        kin = vin = cs = None
+        kv_bs = 0
+    rc = lib.fei_attn_decode_paged_kv8(
+        _ptr(q), _ptr(k_pool.data), _ptr(k_pool.scale), _ptr(v_pool.data),
+        _ptr(v_pool.scale), _ptr(block_table), _ptr(part_o), _ptr(part_ml),
+        _ptr(pos), B, Hq, Hkv, D, BS, block_table.shape[1], splits, scale,
+        q.stride(0), kin, vin, cs, kv_bs, _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_attn_decode_paged_kv8 refused the launch (rc={rc})")
+    lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
+                                B, Hq, D, splits, _stream())
+    return out
+
+
 def rope_kv_prefill_paged(q, k, v, k_pool, v_pool, block_table, pos0,
                           table) -> torch.Tensor:
     """rope_kv_prefill into a PAGED pool: in-place RoPE on q [B,S,Hq,D]; k
@@ -1200,9 +1306,26 @@ def rope_kv_prefill_paged(q, k, v, k_pool, v_pool, block_table, pos0,
 
     Contract on GPU (not checked: it would cost a host sync): block_table
     holds a valid block for every row below max(pos0) + S."""
+    kv8 = _kv8_pair(k_pool, v_pool)
     Hkv, BS = _paged_check("rope_kv_prefill_paged", q, k_pool, block_table,
                            pos0)
     B, S, Hq, D = q.shape
+    if not q.is_cuda and kv8:
+        # the contiguous reference append into scratch rows, then the
+        # appended codes and scales go through the table
+        n = int(pos0.max()) + S if B > 0 else 0
+        kc = QuantKV.zeros((B, Hkv, max(n, 1), D), q.device)
+        vc = QuantKV.zeros((B, Hkv, max(n, 1), D), q.device)
+        q_out = ref.rope_kv_prefill_fp8(q, k, v, kc.data, kc.scale, vc.data,
+                                        vc.scale, pos0, table)
+        for b in range(B):
+            for p in range(int(pos0[b]), int(pos0[b]) + S):
+                _scatter_pool_kv8(k_pool, block_table, b, p,
+                                  kc.data[b, :, p], kc.scale[b, :, p])
+                _scatter_pool_kv8(v_pool, block_table, b, p,
+                                  vc.data[b, :, p], vc.scale[b, :, p])
+        q.copy_(q_out)
+        return q
     if not q.is_cuda:
         n = int(pos0.max()) + S if B > 0 else 0
         kc = k_pool.new_zeros(B, Hkv, max(n, 1), D)
@@ -1221,8 +1344,19 @@ def rope_kv_prefill_paged(q, k, v, k_pool, v_pool, block_table, pos0,
     assert q.stride(0) == S * q.stride(1), "token rows must be uniform"
     assert k.stride(2) == D and k.stride(0) == S * k.stride(1)
     assert k.stride(1) == v.stride(1)
-    assert k_pool.is_contiguous() and v_pool.is_contiguous()
     assert block_table.is_contiguous()
+    if kv8:
+        # (QuantKV asserts its own contiguity and alignment)
+        rc = lib.fei_rope_kv8_prefill_paged(
+            _ptr(q), _ptr(k), _ptr(v), _ptr(k_pool.data), _ptr(k_pool.scale),
+            _ptr(v_pool.data), _ptr(v_pool.scale), _ptr(block_table),
+            _ptr(table), _ptr(pos0), B, S, Hq, Hkv, D, BS,
+            block_table.shape[1], q.stride(1), k.stride(1), _stream())
+        if rc != 0:
+            raise RuntimeError(
+                f"fei_rope_kv8_prefill_paged refused the launch (rc={rc})")
+        return q
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
     rc = lib.fei_rope_kv_prefill_paged(
         _ptr(q), _ptr(k), _ptr(v), _ptr(k_pool), _ptr(v_pool),
         _ptr(block_table), _ptr(table), _ptr(pos0), B, S, Hq, Hkv, D, BS,
@@ -1244,13 +1378,21 @@ def attn_prefill_paged(q, k_pool, v_pool, block_table, pos0,
 
     Contract on GPU (not checked: it would cost a host sync): block_table
     holds a valid block for every row below max(pos0) + S."""
+    kv8 = _kv8_pair(k_pool, v_pool)
     Hkv, BS = _paged_check("attn_prefill_paged", q, k_pool, block_table, pos0)
     B, S, Hq, D = q.shape
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if not q.is_cuda:
         n_rows = [int(pos0[b]) + S for b in range(B)]
-        kc = _gather_pool(k_pool, block_table, n_rows)
-        vc = _gather_pool(v_pool, block_table, n_rows)
+        if kv8:
+            kc = _gather_pool_kv8(k_pool, block_table, n_rows)
+            vc = _gather_pool_kv8(v_pool, block_table, n_rows)
+            if q.dtype == torch.bfloat16:
+                # bf16 run: the kernel stages bf16(f32(code) * scale)
+                kc, vc = kc.to(q.dtype), vc.to(q.dtype)
+        else:
+            kc = _gather_pool(k_pool, block_table, n_rows)
+            vc = _gather_pool(v_pool, block_table, n_rows)
         res = ref.attn_prefill(q, kc, vc, pos0, scale)
         if out is not None:
             out.copy_(res)
@@ -1262,8 +1404,18 @@ def attn_prefill_paged(q, k_pool, v_pool, block_table, pos0,
     assert q.stride(3) == 1 and q.stride(2) == D
     assert q.stride(0) == S * q.stride(1)
     assert out.is_contiguous()
-    assert k_pool.is_contiguous() and v_pool.is_contiguous()
     assert block_table.is_contiguous()
+    if kv8:
+        rc = lib.fei_attn_prefill_paged_kv8(
+            _ptr(q), _ptr(k_pool.data), _ptr(k_pool.scale),
+            _ptr(v_pool.data), _ptr(v_pool.scale), _ptr(block_table),
+            _ptr(out), _ptr(pos0), B, S, Hq, Hkv, D, BS,
+            block_table.shape[1], scale, q.stride(1), _stream())
+        if rc != 0:
+            raise RuntimeError(
+                f"fei_attn_prefill_paged_kv8 refused the launch (rc={rc})")
+        return out
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
     rc = lib.fei_attn_prefill_paged(
         _ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(block_table), _ptr(out),
         _ptr(pos0), B, S, Hq, Hkv, D, BS, block_table.shape[1], scale,

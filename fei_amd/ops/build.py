@@ -15,7 +15,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfei_kernels.so")
 SOURCES = ["fei_kernels.hip", "attn_prefill.hip", "gemv.hip", "attn_decode_fused.hip", "gemv_fp8.hip", "stream_layer.hip",
            "sample_filtered.hip", "kv_fp8.hip", "gemv_addnorm.hip",
-           "attn_prefill_paged.hip"]
+           "attn_prefill_paged.hip", "kv_fp8_paged.hip"]
+HEADERS = ["fei_common.h", "kv_fp8_common.h"]
 HIPCC = os.environ.get("HIPCC", "hipcc")
 ARCH = os.environ.get("FEI_AMD_ARCH", "gfx950")
 
@@ -24,7 +25,7 @@ def needs_build() -> bool:
     if not os.path.exists(OUT):
         return True
     out_mtime = os.path.getmtime(OUT)
-    for src in SOURCES + ["fei_common.h"]:
+    for src in SOURCES + HEADERS:
         if os.path.getmtime(os.path.join(CSRC, src)) > out_mtime:
             return True
     return False

@@ -1,71 +1,51 @@
-// FP8 (OCP e4m3fn) KV cache for gfx950: append, split-K decode attention and
-// MFMA prefill attention over a quantised cache.
+// FP8 (OCP e4m3fn) KV over a PAGED pool for gfx950: the append, split-K
+// decode attention and MFMA prefill attention of kv_fp8.hip with ONE
+// difference — a row is addressed through a block table instead of a
+// contiguous [B,Hkv,max_seq] cache.
 //
-// Storage format (fei_amd/ops/reference.py::quant_kv_fp8 is the definition):
-// each cached row — the D elements of one (batch, kv-head, position) — is D
-// e4m3fn codes plus one f32 scale:
-//   data  u8  [B, Hkv, max_seq, D]       scale f32 [B, Hkv, max_seq]
-//   scale = amax / 448 (1 when amax == 0), code = e4m3fn(x / scale) with an
-//   IEEE f32 division (no fast-math flag in build.py: `/` is correctly
-//   rounded), round-to-nearest-even, saturating.
-// x is what the bf16 cache would have stored: K roped in f32 and rounded to
-// bf16 first, V as given.
+// Pool layer (ops.QuantKV): data u8 [num_blocks, Hkv, BS, D], scale f32
+// [num_blocks, Hkv, BS], BS a power of two (1 included); block_table
+// [B, max_blocks] int32. Logical row p of sequence b is the flat row
+//   row = (bt[b][p >> bs_log] * Hkv + hkv) * BS + (p & (BS-1))
+// which addresses data (x D) and scale alike — the `row` argument of
+// kv8_rope_append (kv_fp8_common.h), so every append path, paged or not,
+// writes identical bytes.
 //
-// The attention kernels are the fp8 counterparts of k_attn_decode
-// (fei_kernels.hip) and k_attn_prefill (attn_prefill.hip): same grids, same
-// LDS layouts, same f32 partials — so k_attn_decode_combine reduces the
-// decode partials unchanged. Codes are dequantised with the hardware
-// converter (v_cvt_pk_f32_fp8); the per-key scale is applied ONCE per key:
-// to the finished K score, and folded into the probability staged for the
-// P*V pass (the running sum l uses the unscaled probability).
-// No kernel reads data or scales at positions >= its valid length.
-// The row quantise/append helper, the G-wide block reduce and the staging
-// dequantiser are shared with the paged kernels: kv_fp8_common.h.
+// Bit identity with the contiguous fp8 kernels is the contract
+// (tests/test_kv_fp8_paged_gpu.py): grids, LDS layouts, lane maps, the
+// chunk = ceil(n / splits) partition, the interleaved key-group V map, the
+// accumulation order and the f32 partials are those of kv_fp8.hip,
+// expression for expression. When one of the two changes, change the other.
+//
+// No kernel reads data or scale of a row at or past its valid length, and no
+// kernel reads the table entry of a block no valid row lives in (production
+// tables pad with -1).
 #include "kv_fp8_common.h"
 
 namespace {
 
-// ---------------------------------------------------------------------------
-// Append, decode form. Grid (Hq+Hkv, B), block 64 (one wave): q heads are
-// roped in place, kv heads are roped + quantised + appended at pos[b].
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(64)
-k_rope_kv8_decode(u16* __restrict__ q, const u16* __restrict__ k,
-                  const u16* __restrict__ v, u8* __restrict__ kd,
-                  float* __restrict__ ks, u8* __restrict__ vd,
-                  float* __restrict__ vs, const float* __restrict__ cos_sin,
-                  const int* __restrict__ pos, int Hq, int Hkv, int D,
-                  int max_seq, long q_bs, long kv_bs) {
-  const int h = blockIdx.x;
-  const int b = blockIdx.y;
-  const int i = threadIdx.x;
-  const int half = D / 2;
-  const int p = pos[b];
-  const float* cs = cos_sin + (long)p * half * 2;
-  if (h < Hq) {
-    if (i < half) {
-      u16* qp = q + (long)b * q_bs + (long)h * D;
-      const float c = cs[i * 2], s = cs[i * 2 + 1];
-      const float x1 = bf2f(qp[i]), x2 = bf2f(qp[i + half]);
-      qp[i] = f2bf(x1 * c - x2 * s);
-      qp[i + half] = f2bf(x2 * c + x1 * s);
-    }
-  } else {
-    const int hk = h - Hq;
-    kv8_rope_append(k + (long)b * kv_bs + (long)hk * D,
-                    v + (long)b * kv_bs + (long)hk * D, cs, D,
-                    ((long)b * Hkv + hk) * max_seq + p, i, kd, ks, vd, vs);
-  }
+// flat pool row of logical row p (bt: the sequence's table row)
+__device__ __forceinline__ long kv8_pool_row(const int* __restrict__ bt, int p,
+                                             int hkv, int Hkv, int bs_log) {
+  const int BS = 1 << bs_log;
+  return ((long)bt[p >> bs_log] * Hkv + hkv) * BS + (p & (BS - 1));
 }
 
-// Append, prefill form: S tokens at pos0[b]+s. Grid (S, Hq+Hkv, B), block 64.
+// ---------------------------------------------------------------------------
+// Append, prefill form: S tokens at logical rows pos0[b]+s, q roped in place.
+// Grid (S, Hq+Hkv, B), block 64: k_rope_kv8_prefill's. Only the kv-head
+// workgroups read the table (one entry, the block row p lives in).
+// ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
-k_rope_kv8_prefill(u16* __restrict__ q, const u16* __restrict__ k,
-                   const u16* __restrict__ v, u8* __restrict__ kd,
-                   float* __restrict__ ks, u8* __restrict__ vd,
-                   float* __restrict__ vs, const float* __restrict__ cos_sin,
-                   const int* __restrict__ pos0, int S, int Hq, int Hkv, int D,
-                   int max_seq, long q_ts, long kv_ts) {
+k_rope_kv8_prefill_paged(u16* __restrict__ q, const u16* __restrict__ k,
+                         const u16* __restrict__ v, u8* __restrict__ kd,
+                         float* __restrict__ ks, u8* __restrict__ vd,
+                         float* __restrict__ vs,
+                         const int* __restrict__ block_table,
+                         const float* __restrict__ cos_sin,
+                         const int* __restrict__ pos0, int S, int Hq, int Hkv,
+                         int D, int bs_log, int max_blocks, long q_ts,
+                         long kv_ts) {
   const int s_idx = blockIdx.x;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
@@ -86,40 +66,40 @@ k_rope_kv8_prefill(u16* __restrict__ q, const u16* __restrict__ k,
     const int hk = h - Hq;
     kv8_rope_append(k + tok * kv_ts + (long)hk * D,
                     v + tok * kv_ts + (long)hk * D, cs, D,
-                    ((long)b * Hkv + hk) * max_seq + p, i, kd, ks, vd, vs);
+                    kv8_pool_row(block_table + (long)b * max_blocks, p, hk,
+                                 Hkv, bs_log),
+                    i, kd, ks, vd, vs);
   }
 }
 
 // ---------------------------------------------------------------------------
-// Split-K decode attention over the fp8 cache. Grid (splits, Hkv, B), block
-// 256; the length n = pos[b]+1 is read on the device. Structure and LDS are
-// those of k_attn_decode; what differs:
-//   phase A: a key row is D bytes (D/16 16-byte loads); the raw score is
-//            multiplied once by k_scale[key].
-//   phase B: ONE V lane map for every chunk length — 8 codes (8 B) per lane,
-//            D/8 lanes per row, and the tile's keys INTERLEAVED over the
-//            256/(D/8) key-groups (key j*kgroups + kg). A wave's four
-//            key-groups then read four adjacent rows (512 contiguous bytes),
-//            and every key-group has work as soon as the chunk holds
-//            `kgroups` keys (16 at D=128), so the bf16 kernel's separate
-//            short-chunk pair map (needed there because its blocked key
-//            assignment idles 15 of 16 groups on a 16-key chunk) has no job
-//            left. p staged in LDS carries v_scale[key].
-// ROPE=true fuses the step's RoPE + KV-append: wave 0 of the split that owns
-// key n-1 quantises and writes the row before the block barrier, then every
-// thread reads it back like any other key (same-workgroup visibility).
-// Always followed by the separate k_attn_decode_combine launch.
+// Split-K decode attention over the fp8 pool: k_attn_decode_kv8 (kv_fp8.hip
+// has the structure notes) with every key's row taken through the table.
+// Grid (splits, Hkv, B), block 256; n = pos[b]+1 read on the device. Phase A
+// looks up one entry per thread (its key), phase B one per key-group trip;
+// both only for keys below `end` <= n. ROPE=true: wave 0 of the split that
+// owns key n-1 ropes, quantises and writes its pool row before the block
+// barrier. Always followed by k_attn_decode_combine.
+//
+// The table lookups and 64-bit pool offsets cost registers over the
+// contiguous kernel; the waves-per-SIMD the contiguous instance reaches is
+// stated so the paged one keeps it (profiles/kv_fp8_paged.md has the
+// figures: no scratch at any G).
 // ---------------------------------------------------------------------------
 template <int G, bool ROPE>
 __global__ void __launch_bounds__(256)
-k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
-                  float* __restrict__ ksc, u8* __restrict__ vd,
-                  float* __restrict__ vsc, float* __restrict__ part_o,
-                  float* __restrict__ part_ml, const int* __restrict__ pos,
-                  int Hq, int Hkv, int D, int max_seq, int splits,
-                  float scale, long q_bs, const u16* __restrict__ kin,
-                  const u16* __restrict__ vin,
-                  const float* __restrict__ cos_sin, long kv_bs) {
+__attribute__((amdgpu_waves_per_eu(G == 8 ? 2 : (G == 1 && !ROPE ? 5 : 4))))
+k_attn_decode_paged_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
+                        float* __restrict__ ksc, u8* __restrict__ vd,
+                        float* __restrict__ vsc,
+                        const int* __restrict__ block_table,
+                        float* __restrict__ part_o,
+                        float* __restrict__ part_ml,
+                        const int* __restrict__ pos, int Hq, int Hkv, int D,
+                        int bs_log, int max_blocks, int splits, float scale,
+                        long q_bs, const u16* __restrict__ kin,
+                        const u16* __restrict__ vin,
+                        const float* __restrict__ cos_sin, long kv_bs) {
   const int split = blockIdx.x;
   const int hkv = blockIdx.y;
   const int b = blockIdx.z;
@@ -149,7 +129,7 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
 
   const int half = D / 2;
   const int p_new = n - 1;
-  const long row0 = ((long)b * Hkv + hkv) * max_seq;
+  const int* bt = block_table + (long)b * max_blocks;
   if (ROPE) {
     const float* cs = cos_sin + (long)p_new * half * 2;
     for (int i = tid; i < G * half; i += blockDim.x) {
@@ -166,7 +146,8 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
     if (p_new >= start && p_new < end && tid < 64)
       kv8_rope_append(kin + (long)b * kv_bs + (long)hkv * D,
                       vin + (long)b * kv_bs + (long)hkv * D, cs, D,
-                      row0 + p_new, tid, kd, ksc, vd, vsc);
+                      kv8_pool_row(bt, p_new, hkv, Hkv, bs_log), tid, kd, ksc,
+                      vd, vsc);
   } else {
     for (int i = tid; i < G * D; i += blockDim.x) {
       const int g = i / D, d = i % D;
@@ -174,11 +155,6 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
     }
   }
   __syncthreads();
-
-  const u8* kbase = kd + row0 * D;
-  const u8* vbase = vd + row0 * D;
-  const float* ksb = ksc + row0;
-  const float* vsb = vsc + row0;
 
   const int dvecs = D / 8;                        // lanes per V row
   const int kgroups = blockDim.x / dvecs;         // 16 at D=128, 32 at D=64
@@ -198,9 +174,10 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
     const int kk = tile + tid;
     float vscale = 0.f;
     if (kk < end) {
-      const u32x4* krow = (const u32x4*)(kbase + (long)kk * D);
-      const float kscale = ksb[kk];
-      vscale = vsb[kk];
+      const long row = kv8_pool_row(bt, kk, hkv, Hkv, bs_log);
+      const u32x4* krow = (const u32x4*)(kd + row * D);
+      const float kscale = ksc[row];
+      vscale = vsc[row];
 #pragma unroll
       for (int g = 0; g < G; ++g) sc[g] = 0.f;
       for (int i = 0; i < D / 16; ++i) {
@@ -255,8 +232,8 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
 #pragma unroll 2
     for (int j = 0; j < iters; ++j) {
       const int kl = j * kgroups + kg;
-      const u32x2 v8 =
-          *((const u32x2*)(vbase + (long)(tile + kl) * D) + dv);
+      const u32x2 v8 = *((const u32x2*)(
+          vd + kv8_pool_row(bt, tile + kl, hkv, Hkv, bs_log) * D) + dv);
       float vf[8];
 #pragma unroll
       for (int w = 0; w < 2; ++w) {
@@ -302,26 +279,30 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
 }
 
 // ---------------------------------------------------------------------------
-// Causal MFMA prefill attention over the fp8 cache: k_attn_prefill<D> with
-// the tile staging changed — 8 codes per slot, dequantised with the key's
-// scale, rounded to bf16 and written to the same swizzled kt / transposed
-// vtT LDS tiles. QK^T / PV MFMA chains and the softmax are the bf16 kernel's.
-// Slots past kv_end are zero-padded without touching data or scales.
-// Everything below the staging block is a copy of k_attn_prefill (kept
-// separate so the bf16 kernel's code and register figures stay untouched):
-// a fix to the softmax, the swizzles or the epilogue there belongs here too.
-// Fragment maps (attn_prefill.hip header, verified by k_mfma_probe):
-//   A[16x32]: lane l -> A[l&15][8*(l>>4)+j], j=0..7
-//   B[32x16]: lane l -> B[8*(l>>4)+j][l&15]
-//   C[16x16]: lane l, reg r -> C[4*(l>>4)+r][l&15]
+// Causal MFMA prefill attention over the fp8 pool: k_attn_prefill_kv8<D>
+// (staging dequantises 8 codes per slot with the key's scale into the same
+// swizzled kt / transposed vtT tiles) plus k_attn_prefill_paged's 64-entry
+// table stage: thread (tid & 63) loads the entry of key t*64 + (tid & 63)
+// ONE TILE AHEAD into a register, right after the staging barrier; wave 0
+// drops the registers into bts in front of the next tile's first barrier and
+// the staging loop reads bts[key]. A key >= kv_end has no entry: its table
+// slot is never read, and neither are its bts slot, codes or scales.
+// Everything below the staging block is k_attn_prefill_kv8's (and so
+// k_attn_prefill's): a fix there belongs here too.
+// LDS: k_attn_prefill_kv8's + 256 B, which changes no workgroups-per-CU
+// count; the waves-per-SIMD target is the contiguous kernel's.
 // ---------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(256)
-k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
-                   const float* __restrict__ ksc, const u8* __restrict__ vd,
-                   const float* __restrict__ vsc, u16* __restrict__ out,
-                   const int* __restrict__ pos0, int S, int Hq, int Hkv,
-                   int max_seq, float scale, long q_ts) {
+__attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 4)))
+k_attn_prefill_paged_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
+                         const float* __restrict__ ksc,
+                         const u8* __restrict__ vd,
+                         const float* __restrict__ vsc,
+                         const int* __restrict__ block_table,
+                         u16* __restrict__ out, const int* __restrict__ pos0,
+                         int S, int Hq, int Hkv, int bs_log, int max_blocks,
+                         float scale, long q_ts) {
   constexpr int DC = D / 16;
   constexpr int KS = D / 32;
   constexpr int KV = 64;
@@ -337,12 +318,7 @@ k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
   const int l15 = lane & 15;
   const int lg = lane >> 4;
 
-  // K tile: row-major, 16-byte slot index XOR-swizzled by (row&7) so the
-  // column-slice ds_read_b128 of a 16-lane group spreads over 8 slots.
-  // V tile: TRANSPOSED [col][key] in 8-key blocks, so the PV B-fragment (8
-  // consecutive keys of one column) is one 16-byte read; the 8-key block
-  // index is XOR-swizzled by (col&7) against the 128-byte column stride's
-  // bank pattern. The transpose is paid in the staging scatter below.
+  // same tiles and swizzles as k_attn_prefill (attn_prefill.hip)
   __shared__ u16 kt[64][D];
   __shared__ u16 vtT[D][64];
   __shared__ u16 p_lds[4][16][64];
@@ -372,16 +348,23 @@ k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
 #pragma unroll
   for (int dc = 0; dc < DC; ++dc) o_acc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long row0 = ((long)b * Hkv + hkv) * max_seq;
-  const u8* kbase = kd + row0 * D;
-  const u8* vbase = vd + row0 * D;
-  const float* ksb = ksc + row0;
-  const float* vsb = vsc + row0;
+  const int BS = 1 << bs_log;
+  const int* bt = block_table + (long)b * max_blocks;
+
+  // physical block of key t*KV + (tid & 63); a key >= kv_end has none
+  __shared__ int bts[KV];
+  int blk_next;
+  auto load_block = [&](int t) {
+    const int kk = t * KV + (tid & 63);
+    blk_next = kk < kv_end ? bt[kk >> bs_log] : 0;
+  };
+  load_block(0);
 
   const int ntiles = (kv_end + KV - 1) / KV;
   for (int t = 0; t < ntiles; ++t) {
     // ---- stage K/V tile: 8 codes per slot -> dequant -> bf16; slots past
     // kv_end are zero and load neither codes nor scales -----------------
+    if (tid < KV) bts[tid] = blk_next;              // read after the barrier
     __syncthreads();                                // vt/kt reuse protection
     {
       const int nv8 = KV * D / 8;
@@ -393,10 +376,11 @@ k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
         s16x8 k8 = {0, 0, 0, 0, 0, 0, 0, 0};
         s16x8 v8 = k8;
         if (kk < kv_end) {
+          const long row = ((long)bts[key] * Hkv + hkv) * BS + (kk & (BS - 1));
           k8 = kv8_dequant8(
-              *(const u32x2*)(kbase + (long)kk * D + col8 * 8), ksb[kk]);
+              *(const u32x2*)(kd + row * D + col8 * 8), ksc[row]);
           v8 = kv8_dequant8(
-              *(const u32x2*)(vbase + (long)kk * D + col8 * 8), vsb[kk]);
+              *(const u32x2*)(vd + row * D + col8 * 8), vsc[row]);
         }
         ((s16x8*)kt)[dst] = k8;
 #pragma unroll
@@ -405,6 +389,7 @@ k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
       }
     }
     __syncthreads();
+    load_block(t + 1);             // past the last tile every key >= kv_end
 
     // ---- QK^T: NC 16-key chunks ---------------------------------------
     f32x4 sfrag[NC];
@@ -496,76 +481,97 @@ k_attn_prefill_kv8(const u16* __restrict__ q, const u8* __restrict__ kd,
 #undef VT_OFF
 }
 
+// log2 of a power-of-two block size, -1 for anything else
+int kv8_block_size_log2(int block_size) {
+  if (block_size <= 0 || (block_size & (block_size - 1)) != 0) return -1;
+  int bs_log = 0;
+  while ((1 << bs_log) < block_size) ++bs_log;
+  return bs_log;
+}
+
 }  // namespace
 
 extern "C" {
 
-void fei_rope_kv8_decode(void* q, const void* k, const void* v, void* kd,
-                         float* ks, void* vd, float* vs, const float* cos_sin,
-                         const int* pos, int B, int Hq, int Hkv, int D,
-                         int max_seq, long q_bs, long kv_bs,
-                         hipStream_t stream) {
-  hipLaunchKernelGGL(k_rope_kv8_decode, dim3(Hq + Hkv, B), dim3(64), 0, stream,
-                     (u16*)q, (const u16*)k, (const u16*)v, (u8*)kd, ks,
-                     (u8*)vd, vs, cos_sin, pos, Hq, Hkv, D, max_seq, q_bs,
-                     kv_bs);
-}
+// All three return 0 when launched and non-zero when they refuse (nothing is
+// launched then): 1 = empty problem (B, S, splits or max_blocks <= 0),
+// 2 = head counts (for decode: a GQA group outside 1/2/4/8), 3 = head size
+// without a kernel instance, 4 = block size not a power of two.
 
-void fei_rope_kv8_prefill(void* q, const void* k, const void* v, void* kd,
-                          float* ks, void* vd, float* vs,
-                          const float* cos_sin, const int* pos0, int B, int S,
-                          int Hq, int Hkv, int D, int max_seq, long q_ts,
-                          long kv_ts, hipStream_t stream) {
-  hipLaunchKernelGGL(k_rope_kv8_prefill, dim3(S, Hq + Hkv, B), dim3(64), 0,
-                     stream, (u16*)q, (const u16*)k, (const u16*)v, (u8*)kd,
-                     ks, (u8*)vd, vs, cos_sin, pos0, S, Hq, Hkv, D, max_seq,
-                     q_ts, kv_ts);
-}
-
-// returns 0, or -1 for an unsupported group size (the wrapper raises)
-int fei_attn_decode_kv8(const void* q, void* kd, float* ks, void* vd,
-                        float* vs, float* part_o, float* part_ml,
-                        const int* pos, int B, int Hq, int Hkv, int D,
-                        int max_seq, int splits, float scale, long q_bs,
-                        const void* kin, const void* vin,
-                        const float* cos_sin, long kv_bs,
-                        hipStream_t stream) {
-  const int G = Hq / Hkv;
-  dim3 grid(splits, Hkv, B);
-  const int rope = cos_sin != nullptr;
-#define LAUNCH_DEC8(GV, RV) \
-  hipLaunchKernelGGL((k_attn_decode_kv8<GV, RV>), grid, dim3(256), 0, stream, \
-                     (const u16*)q, (u8*)kd, ks, (u8*)vd, vs, part_o, \
-                     part_ml, pos, Hq, Hkv, D, max_seq, splits, scale, q_bs, \
-                     (const u16*)kin, (const u16*)vin, cos_sin, kv_bs)
-#define LAUNCH_DEC8_R(GV) do { \
-    if (rope) LAUNCH_DEC8(GV, true); else LAUNCH_DEC8(GV, false); } while (0)
-  switch (G) {
-    case 1: LAUNCH_DEC8_R(1); break;
-    case 2: LAUNCH_DEC8_R(2); break;
-    case 4: LAUNCH_DEC8_R(4); break;
-    case 8: LAUNCH_DEC8_R(8); break;
-    default: return -1;
-  }
-#undef LAUNCH_DEC8_R
-#undef LAUNCH_DEC8
+int fei_rope_kv8_prefill_paged(void* q, const void* k, const void* v,
+                               void* kd, float* ks, void* vd, float* vs,
+                               const int* block_table, const float* cos_sin,
+                               const int* pos0, int B, int S, int Hq, int Hkv,
+                               int D, int block_size, int max_blocks,
+                               long q_ts, long kv_ts, hipStream_t stream) {
+  if (B <= 0 || S <= 0 || max_blocks <= 0) return 1;
+  if (Hq <= 0 || Hkv <= 0) return 2;
+  if (D != 64 && D != 128) return 3;
+  const int bs_log = kv8_block_size_log2(block_size);
+  if (bs_log < 0) return 4;
+  hipLaunchKernelGGL(k_rope_kv8_prefill_paged, dim3(S, Hq + Hkv, B), dim3(64),
+                     0, stream, (u16*)q, (const u16*)k, (const u16*)v, (u8*)kd,
+                     ks, (u8*)vd, vs, block_table, cos_sin, pos0, S, Hq, Hkv,
+                     D, bs_log, max_blocks, q_ts, kv_ts);
   return 0;
 }
 
-int fei_attn_prefill_kv8(const void* q, const void* kd, const float* ks,
-                         const void* vd, const float* vs, void* out,
-                         const int* pos0, int B, int S, int Hq, int Hkv,
-                         int D, int max_seq, float scale, long q_ts,
-                         hipStream_t stream) {
+int fei_attn_decode_paged_kv8(const void* q, void* kd, float* ks, void* vd,
+                              float* vs, const int* block_table,
+                              float* part_o, float* part_ml, const int* pos,
+                              int B, int Hq, int Hkv, int D, int block_size,
+                              int max_blocks, int splits, float scale,
+                              long q_bs, const void* kin, const void* vin,
+                              const float* cos_sin, long kv_bs,
+                              hipStream_t stream) {
+  if (B <= 0 || splits <= 0 || max_blocks <= 0) return 1;
+  if (Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return 2;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return 2;
+  if (D != 64 && D != 128) return 3;
+  const int bs_log = kv8_block_size_log2(block_size);
+  if (bs_log < 0) return 4;
+  dim3 grid(splits, Hkv, B);
+  const int rope = cos_sin != nullptr;
+#define LAUNCH_PDEC8(GV, RV) \
+  hipLaunchKernelGGL((k_attn_decode_paged_kv8<GV, RV>), grid, dim3(256), 0, \
+                     stream, (const u16*)q, (u8*)kd, ks, (u8*)vd, vs, \
+                     block_table, part_o, part_ml, pos, Hq, Hkv, D, bs_log, \
+                     max_blocks, splits, scale, q_bs, (const u16*)kin, \
+                     (const u16*)vin, cos_sin, kv_bs)
+#define LAUNCH_PDEC8_R(GV) do { \
+    if (rope) LAUNCH_PDEC8(GV, true); else LAUNCH_PDEC8(GV, false); } while (0)
+  switch (G) {
+    case 1: LAUNCH_PDEC8_R(1); break;
+    case 2: LAUNCH_PDEC8_R(2); break;
+    case 4: LAUNCH_PDEC8_R(4); break;
+    default: LAUNCH_PDEC8_R(8); break;
+  }
+#undef LAUNCH_PDEC8_R
+#undef LAUNCH_PDEC8
+  return 0;
+}
+
+int fei_attn_prefill_paged_kv8(const void* q, const void* kd, const float* ks,
+                               const void* vd, const float* vs,
+                               const int* block_table, void* out,
+                               const int* pos0, int B, int S, int Hq, int Hkv,
+                               int D, int block_size, int max_blocks,
+                               float scale, long q_ts, hipStream_t stream) {
+  if (B <= 0 || S <= 0 || max_blocks <= 0) return 1;
+  if (Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return 2;
+  if (D != 64 && D != 128) return 3;
+  const int bs_log = kv8_block_size_log2(block_size);
+  if (bs_log < 0) return 4;
   dim3 grid((S + 63) / 64, Hq, B);
-#define LAUNCH_PF8(DV) \
-  hipLaunchKernelGGL(k_attn_prefill_kv8<DV>, grid, dim3(256), 0, stream, \
+#define LAUNCH_PPF8(DV) \
+  hipLaunchKernelGGL(k_attn_prefill_paged_kv8<DV>, grid, dim3(256), 0, stream, \
                      (const u16*)q, (const u8*)kd, ks, (const u8*)vd, vs, \
-                     (u16*)out, pos0, S, Hq, Hkv, max_seq, scale, q_ts)
-  if (D == 128) LAUNCH_PF8(128);
-  else if (D == 64) LAUNCH_PF8(64);
-  else return -1;
-#undef LAUNCH_PF8
+                     block_table, (u16*)out, pos0, S, Hq, Hkv, bs_log, \
+                     max_blocks, scale, q_ts)
+  if (D == 128) LAUNCH_PPF8(128);
+  else LAUNCH_PPF8(64);
+#undef LAUNCH_PPF8
   return 0;
 }
 

@@ -5,7 +5,9 @@ POST /v1/completions        prompt, max_tokens, temperature, top_k, top_p,
                             speculative, cache_prefix
 POST /v1/chat/completions   messages=[{role, content}], ... (+ stream SSE)
 POST /v1/sessions           open a paged continuous-batching session
-POST /v1/sessions/step      advance all sessions (?n=K)
+POST /v1/sessions/step      advance all sessions (?n=K); reports the pool's
+                            free_blocks and kv_dtype ("fp8" when the engine
+                            was created with kv_quant="fp8")
 GET  /v1/sessions/{id}      poll result     DELETE /v1/sessions/{id}  close
 POST /v1/sessions/{id}/extend   continue a finished session (next turn)
 GET  /v1/models             available ModelSpecs
@@ -269,6 +271,8 @@ def create_app(engine: Optional[LocalEngine] = None,
     def _mgr():
         if state["mgr"] is None:
             from fei_amd.engine.sessions import PagedSessionManager
+            # the pool inherits the engine's kv_quant (an fp8 engine serves
+            # its sessions out of fp8 blocks)
             state["mgr"] = PagedSessionManager(eng, num_blocks=session_blocks)
         return state["mgr"]
 
@@ -291,7 +295,8 @@ def create_app(engine: Optional[LocalEngine] = None,
             advanced = mgr.step_chunk(max(1, n))
         return {"active": advanced,
                 "open": len(mgr.sessions),
-                "free_blocks": mgr.pool.free_blocks()}
+                "free_blocks": mgr.pool.free_blocks(),
+                "kv_dtype": mgr.pool.kv_dtype}
 
     @app.get("/v1/sessions/{sid}")
     def session_get(sid: int):
@@ -330,6 +335,7 @@ def create_app(engine: Optional[LocalEngine] = None,
         return {"closed": sid}
 
     app.state.engine = eng
+    app.state.session_manager = _mgr      # callable: built on first use
     return app
 
 

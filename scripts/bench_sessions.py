@@ -1,7 +1,9 @@
 """Continuous-batching serving throughput: N concurrent sessions with
 staggered prompt lengths through PagedSessionManager (block-table
 attention, per-step admission/retire) — the serving-path counterpart of
-bench.py --batch (which measures the static-batch engine loop)."""
+bench.py --batch (which measures the static-batch engine loop).
+--kv-quant fp8 serves the sessions out of an fp8 KV pool."""
+import argparse
 import json
 import os
 import sys
@@ -13,11 +15,18 @@ import torch
 from fei_amd.engine.engine import LocalEngine
 from fei_amd.engine.sessions import PagedSessionManager
 
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument("--kv-quant", choices=["none", "fp8"], default="none",
+                help="KV pool format (default: the unquantised pool)")
+args = ap.parse_args()
+KVQ = None if args.kv_quant == "none" else args.kv_quant
 N = int(os.environ.get("SESS_N", "8"))
 NEW = int(os.environ.get("SESS_NEW", "256"))
 MODEL = os.environ.get("SESS_MODEL", "llama3-8b")
 eng = LocalEngine.create(MODEL, max_seq_len=4096, seed=7)
-mgr = PagedSessionManager(eng)
+# the engine (and so the memory left for the pool) is the same in both modes:
+# only the pool's format changes
+mgr = PagedSessionManager(eng, kv_quant=KVQ)
 rng = torch.Generator().manual_seed(5)
 sids = []
 for i in range(N):
@@ -43,4 +52,5 @@ print(json.dumps({
     "value": round(toks / dt, 1), "unit": "tok/s", "sessions": N,
     "new_tokens_per_session": NEW, "steps": steps,
     "ms_per_step": round(dt / steps * 1000, 3), "model": MODEL,
+    "kv_dtype": mgr.pool.kv_dtype, "pool_blocks": mgr.pool.num_blocks,
     "data": "synthetic"}))
