@@ -12,6 +12,11 @@ Prompts are prefilled straight into the session's blocks
 `k_attn_prefill_paged`), and a finished session can be continued with new
 prompt tokens (`extend`: a tool result, the next user message) without
 re-prefilling the conversation: open -> step -> result -> extend -> step ...
+Several admissions at once (agents that start together, tool results that
+come back together) share packed ragged forwards instead of paying one
+forward each: `open_many` / `extend_many` over
+`LlamaModel.forward_prefill_paged_ragged` (`k_rope_kv_prefill_paged_ragged`
++ `k_attn_prefill_paged_ragged`), all or nothing on pool exhaustion.
 
 The pool follows the engine's KV format: on an engine built with
 ``kv_quant="fp8"`` (or with an explicit ``kv_quant="fp8"`` here) the sessions
@@ -84,6 +89,7 @@ class PagedSessionManager:
         self.sessions: Dict[int, Session] = {}
         self.eos = engine.tokenizer.eos_id
         self._ws: Dict[int, tuple] = {}     # split-K workspace per batch size
+        self._serial_logged = False         # fp8 batched-admission notice
         # hipGraph per (B, table_width): one captured decode step (forward
         # + argmax feedback + pos advance) over static buffers. Measured
         # NEUTRAL (836 vs 869 tok/s eager at 8 sessions): the eager chunk
@@ -251,6 +257,187 @@ class PagedSessionManager:
         s.turn += 1
         s.done = first == self.eos
         return first
+
+    # -- batched admission ----------------------------------------------------
+
+    def _ids(self, prompt: Union[str, List[int]]) -> List[int]:
+        return (self.engine.tokenizer.encode(prompt)
+                if isinstance(prompt, str) else list(prompt))
+
+    def _ragged_admission(self) -> bool:
+        """False for an fp8 pool on the GPU: there is no fp8 ragged kernel,
+        so open_many / extend_many admit one session per forward there."""
+        if self.pool.kv_quant == "fp8" and self.model.device.type == "cuda":
+            if not self._serial_logged:
+                logger.info("fp8 KV pool: batched admission runs one "
+                            "session per forward (no fp8 ragged prefill "
+                            "kernel)")
+                self._serial_logged = True
+            return False
+        return True
+
+    def open_many(self, prompts, max_new_tokens: int = 256,
+                  max_batch_tokens: Optional[int] = None) -> List[int]:
+        """open() for several prompts at once; returns their session ids in
+        order. The prompts share packed ragged prefill forwards
+        (LlamaModel.forward_prefill_paged_ragged) instead of paying one
+        forward each; see _prefill_many for the schedule. Every session ends
+        up exactly as open() would leave it.
+
+        All or nothing: blocks for every prompt are reserved first, and when
+        the pool runs out MemoryError is raised with the sessions, every
+        block list and the free list exactly as before the call."""
+        all_ids = [self._ids(p) for p in prompts]
+        if any(not ids for ids in all_ids):
+            raise ValueError("open_many: empty prompt")
+        if not all_ids:
+            return []
+        sids: List[int] = []
+
+        def rollback():
+            for sid in reversed(sids):
+                self.pool.truncate(sid, 0)      # undoes the take order
+                self.pool.release(sid)
+
+        try:
+            for ids in all_ids:
+                sids.append(self.pool.new_sequence())
+                self.pool.ensure_capacity(sids[-1], len(ids) + 1)
+        except MemoryError:
+            rollback()
+            raise
+        if not self._ragged_admission():
+            rollback()                          # open() takes the same blocks
+            return [self.open(ids, max_new_tokens) for ids in all_ids]
+        firsts = self._prefill_many(
+            [(sid, ids, 0) for sid, ids in zip(sids, all_ids)],
+            max_batch_tokens)
+        for sid, ids, first in zip(sids, all_ids, firsts):
+            self.sessions[sid] = Session(
+                sid=sid, prompt_ids=ids, generated=[first], pos=len(ids),
+                max_new_tokens=max_new_tokens, done=first == self.eos,
+                context_ids=list(ids))
+        return sids
+
+    def extend_many(self, items, max_new_tokens: int = 256,
+                    max_batch_tokens: Optional[int] = None) -> List[int]:
+        """extend() for several finished sessions at once: ``items`` are
+        (sid, prompt) pairs; returns the first token of every new turn, in
+        order. The extensions share packed ragged prefill forwards.
+
+        Everything is validated before anything is touched, with extend()'s
+        errors (KeyError unknown session; ValueError still active, or the
+        context would exceed max_seq_len) and ValueError for a session that
+        appears twice. Then all or nothing: MemoryError leaves every session,
+        block list, length and the free list exactly as before the call."""
+        todo = []
+        seen = set()
+        for sid, prompt in items:
+            s = self.sessions[sid]                  # KeyError: unknown
+            if sid in seen:
+                raise ValueError(f"session {sid} appears twice")
+            seen.add(sid)
+            if not s.done:
+                raise ValueError(f"session {sid} is still active")
+            new_ids = self._ids(prompt)
+            n = 1 + len(new_ids)
+            if s.pos + n + max_new_tokens > self.model.max_seq_len:
+                raise ValueError(
+                    f"session {sid}: context {s.pos} + {n} new + "
+                    f"{max_new_tokens} to generate exceeds max_seq_len "
+                    f"{self.model.max_seq_len}")
+            todo.append((s, new_ids))
+        if not todo:
+            return []
+        grown = []                                  # (sid, blocks held, length)
+
+        def rollback():
+            for sid, held, length in reversed(grown):
+                self.pool.truncate(sid, held * self.pool.block_size)
+                self.pool.table(sid).length = length
+
+        try:
+            for s, new_ids in todo:
+                t = self.pool.table(s.sid)
+                grown.append((s.sid, len(t.blocks), t.length))
+                self.pool.ensure_capacity(s.sid, s.pos + 1 + len(new_ids) + 1)
+        except MemoryError:
+            rollback()
+            raise
+        if not self._ragged_admission():
+            rollback()                              # extend() grows them again
+            return [self.extend(s.sid, new_ids, max_new_tokens)
+                    for s, new_ids in todo]
+        firsts = self._prefill_many(
+            [(s.sid, [s.generated[-1]] + new_ids, s.pos)
+             for s, new_ids in todo], max_batch_tokens)
+        for (s, new_ids), first in zip(todo, firsts):
+            s.context_ids = s.context_ids + self._emitted(s) + new_ids
+            s.pos += 1 + len(new_ids)
+            s.generated = [first]
+            s.max_new_tokens = max_new_tokens
+            s.turn += 1
+            s.done = first == self.eos
+        return firsts
+
+    def _prefill_many(self, work, max_batch_tokens: Optional[int]
+                      ) -> List[int]:
+        """Prefill ``work`` = [(sid, ids, pos0)] into blocks already
+        reserved; returns every item's first token (greedy).
+
+        Schedule: each item is cut into the pieces _prefill_paged would cut
+        it into (LocalEngine.PREFILL_CHUNK tokens from its own start). A
+        forward takes the next piece of every unfinished item, in order, as
+        long as it stays within ``max_batch_tokens`` tokens (default
+        PREFILL_CHUNK) — at most one piece per item, since a later piece
+        attends the rows its predecessor writes; an item's later pieces go
+        into later forwards with pos0 advanced. A forward always takes at
+        least one piece, so a budget below the piece size degrades to one
+        piece per forward. One host sync per forward (the argmax download),
+        and only in forwards that finish an item."""
+        m, dev = self.model, self.model.device
+        chunk = self.engine.PREFILL_CHUNK
+        budget = chunk if max_batch_tokens is None else int(max_batch_tokens)
+        if budget < 1:
+            raise ValueError(f"max_batch_tokens must be >= 1, got {budget}")
+        done_at = [0] * len(work)                   # tokens prefilled so far
+        firsts: List[Optional[int]] = [None] * len(work)
+        blocks = [self.pool.table(sid).blocks for sid, _, _ in work]
+        while any(d < len(w[1]) for d, w in zip(done_at, work)):
+            take, used = [], 0                      # (item, piece length)
+            for i, (_, ids, _) in enumerate(work):
+                left = len(ids) - done_at[i]
+                if left <= 0:
+                    continue
+                n = min(chunk, left)
+                if take and used + n > budget:
+                    continue
+                take.append((i, n))
+                used += n
+            width = max(len(blocks[i]) for i, _ in take)
+            table = torch.full((len(take), width), -1, dtype=torch.int32)
+            flat: List[int] = []
+            for row, (i, n) in enumerate(take):
+                table[row, :len(blocks[i])] = torch.tensor(blocks[i],
+                                                           dtype=torch.int32)
+                flat += work[i][1][done_at[i]:done_at[i] + n]
+            batch = ops.RaggedBatch(
+                [n for _, n in take],
+                [work[i][2] + done_at[i] for i, _ in take], table, dev,
+                block_size=self.pool.block_size)
+            tokens = torch.tensor(flat, dtype=torch.int64, device=dev)
+            logits = m.forward_prefill_paged_ragged(tokens, batch,
+                                                    self.pool.k, self.pool.v)
+            finished = []
+            for row, (i, n) in enumerate(take):
+                done_at[i] += n
+                if done_at[i] == len(work[i][1]):
+                    finished.append((row, i))
+            if finished:
+                top = logits.argmax(dim=-1).tolist()        # the one sync
+                for row, i in finished:
+                    firsts[i] = int(top[row])
+        return firsts
 
     def _emitted(self, s: Session) -> List[int]:
         """The current turn's tokens, cut at the first EOS (inclusive)."""

@@ -453,10 +453,45 @@ class LlamaModel:
 
         return self._prefill_layers(tokens, attend, all_positions)
 
-    def _prefill_layers(self, tokens, attend, all_positions):
+    def forward_prefill_paged_ragged(
+        self,
+        tokens: torch.Tensor,         # [T] packed tokens of all sequences
+        batch,                        # ops.RaggedBatch of this forward
+        k_pools: List,                # per layer [num_blocks, Hkv, BS, D]
+        v_pools: List,
+    ) -> torch.Tensor:
+        """One prefill forward for SEVERAL sequences of unequal length over
+        a paged KV pool: the tokens are packed back to back ([T], T =
+        sum(len_b)), the GEMMs run on all T rows at once and the append and
+        the attention go through ops.rope_kv_prefill_paged_ragged /
+        ops.attn_prefill_paged_ragged with ``batch`` (sequence bounds, pos0
+        and block table). Returns [B, vocab], the logits at every sequence's
+        last token; the vocab GEMM runs on those B rows only. tp = 1 only."""
+        if self.tp_size != 1:
+            raise RuntimeError(
+                "forward_prefill_paged_ragged is single-GPU (tp=1)")
+        if tokens.dim() != 1 or tokens.shape[0] != batch.T:
+            raise ValueError(f"tokens must be [T={batch.T}], got "
+                             f"{tuple(tokens.shape)}")
+        scale = 1.0 / math.sqrt(self.D)
+
+        def attend(li, q, k, v):
+            ops.rope_kv_prefill_paged_ragged(q[0], k[0], v[0], k_pools[li],
+                                             v_pools[li], batch, self.rope)
+            return ops.attn_prefill_paged_ragged(q[0], k_pools[li],
+                                                 v_pools[li], batch,
+                                                 scale=scale)
+
+        return self._prefill_layers(tokens.unsqueeze(0), attend, False,
+                                    keep=batch.last_index)
+
+    def _prefill_layers(self, tokens, attend, all_positions, keep=None):
         """The prefill layer stack; ``attend(li, q, k, v)`` appends layer
         li's K/V rows (roping q in place) and returns the attention output
-        [B, S, Hq, D]."""
+        [B, S, Hq, D] (or anything that reshapes to [B, S, Hq*D]). ``keep``:
+        int64 indices into the B*S rows whose logits are wanted — only they
+        go through the lm_head GEMM ([len(keep), vocab]); None keeps the
+        last position of every batch row (or all, with all_positions)."""
         s = self.spec
         B, S = tokens.shape
         h = F.embedding(tokens.long(), self.emb)          # [B,S,C] residual
@@ -477,7 +512,10 @@ class LlamaModel:
             next_norm = (self.layers[li + 1].norm_attn if li + 1 < n_layers
                          else self.norm_f)
             x, h = ops.fused_add_rmsnorm(d, h, next_norm, s.norm_eps)
-        last = x if all_positions else x[:, -1, :]
+        if keep is not None:
+            last = x.reshape(B * S, -1)[keep]
+        else:
+            last = x if all_positions else x[:, -1, :]
         logits = F.linear(last, self.lm_head)
         logits = all_gather_cat(logits, dim=-1, ctx=self.tp)
         return logits

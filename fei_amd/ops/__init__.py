@@ -108,6 +108,14 @@ def _try_load() -> None:
         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
         _i, _i, _i, _i, _i, _i, _i, _f, _l, _vp]
     lib.fei_attn_prefill_paged_kv8.restype = _i
+    lib.fei_rope_kv_prefill_paged_ragged.argtypes = [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+        _i, _i, _i, _i, _i, _i, _i, _l, _l, _vp]
+    lib.fei_rope_kv_prefill_paged_ragged.restype = _i
+    lib.fei_attn_prefill_paged_ragged.argtypes = [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+        _i, _i, _i, _i, _i, _i, _i, _i, _f, _l, _vp]
+    lib.fei_attn_prefill_paged_ragged.restype = _i
     lib.fei_add_layernorm.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _f,
                                       _i, _vp]
     lib.fei_gelu.argtypes = [_vp, _vp, _l, _vp]
@@ -1423,6 +1431,214 @@ def attn_prefill_paged(q, k_pool, v_pool, block_table, pos0,
     if rc != 0:
         raise RuntimeError(
             f"fei_attn_prefill_paged refused the launch (rc={rc})")
+    return out
+
+
+# -- ragged prefill over a paged KV pool (csrc/attn_prefill_ragged.hip) ------
+
+class RaggedBatch:
+    """The host-built description of ONE packed prefill forward over a paged
+    pool: B sequences of seq_lens[b] tokens, packed back to back (T tokens),
+    sequence b's row s being logical KV row pos0[b] + s behind row b of
+    block_table [B, W] int32. Built once per forward and reused by every
+    layer's rope_kv_prefill_paged_ragged / attn_prefill_paged_ragged.
+
+    On the device: ``cu_seqlens`` int32 [B+1]; ``tile_map`` int32
+    [n_tiles, 2], the (sequence, 64-row q tile) work list of the attention
+    kernel, n_tiles = sum(ceil(len_b / 64)); ``tok_seq`` int32 [T], each
+    packed token's sequence (the append kernel's lookup); ``pos0`` int32 [B];
+    ``block_table``; ``last_index`` int64 [B], the packed row of every
+    sequence's last token. The four int32 arrays are slices of one buffer:
+    one upload. ``seq_lens`` and ``pos0_host`` stay as host lists.
+
+    ``block_size``, when given, checks the table's width here; the ops check
+    it against their pool in any case (host integers only, no sync)."""
+
+    Q_TILE = 64
+
+    def __init__(self, seq_lens, pos0, block_table, device,
+                 block_size: Optional[int] = None):
+        seq_lens = [int(n) for n in seq_lens]
+        pos0 = [int(p) for p in pos0]
+        if not seq_lens:
+            raise ValueError("RaggedBatch: no sequences")
+        if len(seq_lens) != len(pos0):
+            raise ValueError(
+                f"RaggedBatch: {len(seq_lens)} lengths, {len(pos0)} pos0")
+        if min(seq_lens) < 1:
+            raise ValueError(
+                f"RaggedBatch: every length must be >= 1, got {seq_lens}")
+        if min(pos0) < 0:
+            raise ValueError(f"RaggedBatch: negative pos0 in {pos0}")
+        B = len(seq_lens)
+        if not torch.is_tensor(block_table) or block_table.dim() != 2 or \
+                block_table.shape[0] != B or \
+                block_table.dtype != torch.int32:
+            raise ValueError("RaggedBatch: block_table must be int32 "
+                             f"[B={B}, max_blocks]")
+        self.seq_lens, self.pos0_host = seq_lens, pos0
+        self.B = B
+        self.max_blocks = int(block_table.shape[1])
+        if block_size is not None:
+            self.check_table("RaggedBatch", int(block_size))
+        cu = [0]
+        for n in seq_lens:
+            cu.append(cu[-1] + n)
+        self.T = T = cu[-1]
+        tiles, tok_seq = [], []
+        for b, n in enumerate(seq_lens):
+            for qt in range(-(-n // self.Q_TILE)):
+                tiles += [b, qt]
+            tok_seq += [b] * n
+        self.n_tiles = len(tiles) // 2
+        device = torch.device(device)
+        self.device = device
+        packed = torch.tensor(cu + tiles + tok_seq + pos0,
+                              dtype=torch.int32).to(device)
+        a, b_, c = B + 1, B + 1 + len(tiles), B + 1 + len(tiles) + T
+        self.cu_seqlens = packed[:a]
+        self.tile_map = packed[a:b_].view(self.n_tiles, 2)
+        self.tok_seq = packed[b_:c]
+        self.pos0 = packed[c:]
+        self.block_table = block_table.to(device).contiguous()
+        self.last_index = torch.tensor([e - 1 for e in cu[1:]],
+                                       dtype=torch.int64).to(device)
+        self._cu_host = cu
+
+    def rows(self, b: int) -> slice:
+        """The packed rows of sequence b."""
+        return slice(self._cu_host[b], self._cu_host[b + 1])
+
+    def check_table(self, name: str, BS: int) -> None:
+        """ValueError when the table is narrower than a sequence needs."""
+        if BS <= 0 or BS & (BS - 1):
+            raise ValueError(f"{name}: block size must be a power of two, "
+                             f"got {BS}")
+        for b, (n, p) in enumerate(zip(self.seq_lens, self.pos0_host)):
+            need = -(-(p + n) // BS)
+            if self.max_blocks < need:
+                raise ValueError(
+                    f"{name}: block_table has {self.max_blocks} entries per "
+                    f"row, sequence {b} (pos0 {p} + {n} rows, block size "
+                    f"{BS}) needs {need}")
+
+
+def _ragged_check(name: str, q, k_pool, batch: RaggedBatch) -> Tuple[int, int]:
+    """Shared argument checks of the ragged paged ops; returns (Hkv, BS)."""
+    if q.dim() != 3 or q.shape[0] != batch.T:
+        raise ValueError(f"{name}: q must be [T={batch.T}, Hq, D], got "
+                         f"{tuple(q.shape)}")
+    _, Hq, D = q.shape
+    Hkv, BS = k_pool.shape[1], k_pool.shape[2]
+    if Hkv <= 0 or Hq % Hkv != 0:
+        raise ValueError(f"{name}: Hq={Hq} is not a multiple of Hkv={Hkv}")
+    if BS <= 0 or BS & (BS - 1):
+        raise ValueError(f"{name}: block size must be a power of two, "
+                         f"got {BS}")
+    if q.is_cuda and D not in (64, 128):
+        raise ValueError(f"{name} supports D in (64,128), got {D}")
+    batch.check_table(name, BS)
+    if batch.device != q.device:
+        raise ValueError(f"{name}: batch lives on {batch.device}, q on "
+                         f"{q.device}")
+    return Hkv, BS
+
+
+def rope_kv_prefill_paged_ragged(q, k, v, k_pool, v_pool, batch: RaggedBatch,
+                                 table) -> torch.Tensor:
+    """rope_kv_prefill_paged for a PACKED batch: in-place RoPE on q
+    [T, Hq, D]; k [T, Hkv, D] roped + v appended at logical row pos0[b] + s of
+    sequence b for packed row cu[b] + s, through row b of batch.block_table.
+    ``table`` is the RoPE cos/sin table. Per sequence the rows are bit-equal
+    to rope_kv_prefill_paged's on that sequence alone.
+
+    CPU tensors: the uniform op's reference dispatch, sequence by sequence
+    (fp8 pools included). GPU: k_rope_kv_prefill_paged_ragged; an fp8 pool
+    has no ragged kernel and raises NotImplementedError."""
+    kv8 = _kv8_pair(k_pool, v_pool)
+    name = "rope_kv_prefill_paged_ragged"
+    Hkv, BS = _ragged_check(name, q, k_pool, batch)
+    T, Hq, D = q.shape
+    if not q.is_cuda:
+        for b in range(batch.B):
+            r = batch.rows(b)
+            rope_kv_prefill_paged(
+                q[r].unsqueeze(0), k[r].unsqueeze(0), v[r].unsqueeze(0),
+                k_pool, v_pool, batch.block_table[b:b + 1],
+                batch.pos0[b:b + 1], table)
+        return q
+    if kv8:
+        raise NotImplementedError(
+            f"{name}: no ragged kernel for an fp8 pool; admit serially "
+            "(rope_kv_prefill_paged)")
+    lib = require_lib()
+    assert q.stride(2) == 1 and q.stride(1) == D
+    assert k.stride(2) == 1 and k.stride(1) == D
+    assert v.stride(2) == 1 and v.stride(1) == D
+    assert k.stride(0) == v.stride(0)
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    rc = lib.fei_rope_kv_prefill_paged_ragged(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(k_pool), _ptr(v_pool),
+        _ptr(batch.block_table), _ptr(table), _ptr(batch.pos0),
+        _ptr(batch.cu_seqlens), _ptr(batch.tok_seq), T, batch.B, Hq, Hkv, D,
+        BS, batch.max_blocks, q.stride(0), k.stride(0), _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_rope_kv_prefill_paged_ragged refused the launch (rc={rc})")
+    return q
+
+
+def attn_prefill_paged_ragged(q, k_pool, v_pool, batch: RaggedBatch,
+                              scale: Optional[float] = None,
+                              out: Optional[torch.Tensor] = None
+                              ) -> torch.Tensor:
+    """attn_prefill_paged for a PACKED batch: packed q row cu[b] + s (roped)
+    attends the logical rows [0, pos0[b] + s] of sequence b. q [T, Hq, D];
+    returns (or fills the first T rows of) out [T, Hq, D]. One launch over a
+    (sequence, q tile) work list; per sequence the rows are bit-equal to
+    attn_prefill_paged's on that sequence alone. No table entry of a block
+    at or past ceil((pos0[b] + len_b) / BS) is read.
+
+    CPU tensors: the uniform op's reference dispatch, sequence by sequence
+    (fp8 pools included). GPU: k_attn_prefill_paged_ragged<D>; an fp8 pool
+    raises NotImplementedError."""
+    kv8 = _kv8_pair(k_pool, v_pool)
+    name = "attn_prefill_paged_ragged"
+    Hkv, BS = _ragged_check(name, q, k_pool, batch)
+    T, Hq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if out is not None and (out.dim() != 3 or out.shape[0] < T or
+                            tuple(out.shape[1:]) != (Hq, D)):
+        raise ValueError(f"{name}: out must be [>= {T}, {Hq}, {D}], got "
+                         f"{tuple(out.shape)}")
+    if not q.is_cuda:
+        if out is None:
+            out = torch.empty(T, Hq, D, dtype=q.dtype)
+        for b in range(batch.B):
+            r = batch.rows(b)
+            out[r] = attn_prefill_paged(
+                q[r].unsqueeze(0), k_pool, v_pool,
+                batch.block_table[b:b + 1], batch.pos0[b:b + 1],
+                scale=scale)[0]
+        return out
+    if kv8:
+        raise NotImplementedError(
+            f"{name}: no ragged kernel for an fp8 pool; admit serially "
+            "(attn_prefill_paged)")
+    lib = require_lib()
+    if out is None:
+        out = torch.empty(T, Hq, D, dtype=q.dtype, device=q.device)
+    assert q.stride(2) == 1 and q.stride(1) == D
+    assert out.is_contiguous() and out.dtype == q.dtype
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    rc = lib.fei_attn_prefill_paged_ragged(
+        _ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(batch.block_table),
+        _ptr(out), _ptr(batch.pos0), _ptr(batch.cu_seqlens),
+        _ptr(batch.tile_map), batch.n_tiles, T, batch.B, Hq, Hkv, D, BS,
+        batch.max_blocks, scale, q.stride(0), _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"fei_attn_prefill_paged_ragged refused the launch (rc={rc})")
     return out
 
 

@@ -5,6 +5,8 @@ POST /v1/completions        prompt, max_tokens, temperature, top_k, top_p,
                             speculative, cache_prefix
 POST /v1/chat/completions   messages=[{role, content}], ... (+ stream SSE)
 POST /v1/sessions           open a paged continuous-batching session
+POST /v1/sessions/batch     open several sessions in shared ragged prefill
+                            forwards (prompts=[...]); all or nothing
 POST /v1/sessions/step      advance all sessions (?n=K); reports the pool's
                             free_blocks and kv_dtype ("fp8" when the engine
                             was created with kv_quant="fp8")
@@ -56,6 +58,11 @@ class ChatMessage(BaseModel):
 
 class SessionOpen(BaseModel):
     prompt: str
+    max_tokens: int = 256
+
+
+class SessionOpenBatch(BaseModel):
+    prompts: List[str]
     max_tokens: int = 256
 
 
@@ -285,6 +292,24 @@ def create_app(engine: Optional[LocalEngine] = None,
             except MemoryError as e:
                 raise HTTPException(status_code=503, detail=str(e))
         return {"session_id": sid}
+
+    @app.post("/v1/sessions/batch")
+    def session_open_batch(req: SessionOpenBatch):
+        """Open several sessions in shared ragged prefill forwards
+        (PagedSessionManager.open_many): 400 on an empty list or an empty
+        prompt, 503 on pool exhaustion with NOTHING admitted."""
+        from fastapi import HTTPException
+        if not req.prompts:
+            raise HTTPException(status_code=400, detail="prompts is empty")
+        with lock:
+            try:
+                sids = _mgr().open_many(req.prompts,
+                                        max_new_tokens=req.max_tokens)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            except MemoryError as e:
+                raise HTTPException(status_code=503, detail=str(e))
+        return {"session_ids": sids}
 
     @app.post("/v1/sessions/step")
     def session_step(n: int = 1):

@@ -12,10 +12,15 @@
    llama3-8b, against the scratch-cache + slice-copy admission it replaced
    (kept here, as open_scatter, for this comparison only). Host clock around
    a call that ends in a device synchronise; the two alternate.
+3. Ragged (profiles/ragged_prefill.md): ONE ops.attn_prefill_paged_ragged
+   launch over B packed sequences against B separate ops.attn_prefill_paged
+   launches on the same sequences, pool and tables: 8 x 256 tokens, and a
+   ragged mix. Bit-equal per sequence before anything is timed; timed as in 1.
 
 Needs a GPU: there is no CPU fallback for a timing.
 
-    python scripts/bench_paged_prefill.py [--skip-open] [--out FILE]
+    python scripts/bench_paged_prefill.py [--skip-open] [--ragged-only]
+                                          [--out FILE]
 """
 
 from __future__ import annotations
@@ -101,6 +106,88 @@ def bench_kernel(S: int, pos0: int, launches: int, rounds: int) -> dict:
             "paged_tflops": round(flops / mp / 1e6, 1)}
 
 
+RAGGED_SHAPES = [([256] * 8, [0] * 8, 100),
+                 ([40, 1500, 256, 64, 700, 128, 40, 300], [0] * 8, 50),
+                 ([40, 17, 256, 64, 3, 128, 40, 300],
+                  [1500, 700, 0, 2048, 300, 64, 40, 1000], 100)]
+
+
+def bench_ragged(lens, pos0, launches: int, rounds: int) -> dict:
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(sum(lens) + sum(pos0))
+    B, T = len(lens), sum(lens)
+    need = [-(-(p + n) // BS) for n, p in zip(lens, pos0)]
+    nb = sum(need)
+    perm = torch.randperm(nb + 8, generator=g)[:nb]
+    kp = torch.randn(nb + 8, HKV, BS, D, generator=g).to(torch.bfloat16) \
+        .to(dev)
+    vp = torch.randn(nb + 8, HKV, BS, D, generator=g).to(torch.bfloat16) \
+        .to(dev)
+    table = torch.full((B, max(need)), -1, dtype=torch.int32)
+    at = 0
+    for b, n in enumerate(need):
+        table[b, :n] = perm[at:at + n].to(torch.int32)
+        at += n
+    table = table.to(dev)
+    q = torch.randn(T, HQ, D, generator=g).to(torch.bfloat16).to(dev)
+    batch = ops.RaggedBatch(lens, pos0, table, dev, block_size=BS)
+    scale = 1.0 / math.sqrt(D)
+    out_r = torch.empty_like(q)
+    out_s = torch.empty_like(q)
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    parts = [(q[cu[b]:cu[b + 1]].unsqueeze(0),
+              out_s[cu[b]:cu[b + 1]].unsqueeze(0), table[b:b + 1].contiguous(),
+              torch.full((1,), pos0[b], dtype=torch.int32, device=dev))
+             for b in range(B)]
+
+    def ragged():
+        ops.attn_prefill_paged_ragged(q, kp, vp, batch, scale=scale,
+                                      out=out_r)
+
+    def serial():
+        for qb, ob, tb, pb in parts:
+            ops.attn_prefill_paged(qb, kp, vp, tb, pb, scale=scale, out=ob)
+
+    for _ in range(5):
+        ragged()
+        serial()
+    torch.cuda.synchronize()
+    if not torch.equal(out_r.view(torch.int16), out_s.view(torch.int16)):
+        raise SystemExit(f"lens={lens} pos0={pos0}: ragged output differs")
+
+    def timed(fn) -> float:
+        a, b = torch.cuda.Event(enable_timing=True), \
+            torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / launches   # us per call (B launches
+                                                    # for the serial form)
+
+    ts, tr = [], []
+    for _ in range(rounds):
+        ts.append(timed(serial))
+        tr.append(timed(ragged))
+    flops = 0.0
+    for n, p in zip(lens, pos0):
+        flops += 4.0 * D * HQ * (n * p + n * (n + 1) / 2)
+    ms, mr = statistics.median(ts), statistics.median(tr)
+    return {"what": "attn_prefill_paged_ragged vs B x attn_prefill_paged",
+            "lens": lens, "pos0": pos0, "tiles": batch.n_tiles,
+            "launches_per_round": launches, "rounds": rounds,
+            "serial_us": round(ms, 2), "serial_us_min_max":
+            [round(min(ts), 2), round(max(ts), 2)],
+            "ragged_us": round(mr, 2), "ragged_us_min_max":
+            [round(min(tr), 2), round(max(tr), 2)],
+            "ragged_over_serial": round(mr / ms, 4),
+            "serial_tflops": round(flops / ms / 1e6, 1),
+            "ragged_tflops": round(flops / mr / 1e6, 1)}
+
+
 def open_scatter(mgr, ids) -> int:
     """The admission open() used before the paged prefill kernels: prefill
     into a contiguous scratch cache per layer, then copy it into the
@@ -175,15 +262,21 @@ def main(argv=None) -> int:
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--open-rounds", type=int, default=5)
     ap.add_argument("--skip-open", action="store_true")
+    ap.add_argument("--ragged-only", action="store_true",
+                    help="only the ragged section")
     ap.add_argument("--out", default=None, help="also append the JSON lines "
                     "to this file")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_paged_prefill needs a GPU")
     ops.require_lib()
-    results = [bench_kernel(S, p0, n, args.rounds)
-               for S, p0, n in KERNEL_SHAPES]
-    if not args.skip_open:
+    results = []
+    if not args.ragged_only:
+        results += [bench_kernel(S, p0, n, args.rounds)
+                    for S, p0, n in KERNEL_SHAPES]
+    results += [bench_ragged(lens, p0, n, args.rounds)
+                for lens, p0, n in RAGGED_SHAPES]
+    if not args.skip_open and not args.ragged_only:
         results.append(bench_open(2048, args.open_rounds))
     for r in results:
         line = json.dumps(r)
