@@ -14,7 +14,9 @@ mgr = PagedSessionManager(engine, block_size=16, num_blocks=256)
 sids = [mgr.open(p, max_new_tokens=32) for p in
         ["def quicksort(xs):", "SELECT name FROM users WHERE", "# TODO:"]]
 mgr.step(); mgr.step()
-late = mgr.open("print('joined mid-flight')", max_new_tokens=16)
+# a session samples with its own parameters, whoever else is in the batch
+late = mgr.open("print('joined mid-flight')", max_new_tokens=16,
+                temperature=0.8, top_k=50, top_p=0.9, seed=7)
 mgr.run()
 
 for sid in sids + [late]:

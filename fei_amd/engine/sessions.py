@@ -28,8 +28,17 @@ layers) and every read and write goes through the fp8 paged kernels
 Control-plane costs stay host-side (per-step RoPE/append scatter is a few
 microseconds of torch indexing per layer); the O(context) work — attention
 over the pool — is the paged HIP kernel, and all GEMVs take the same
-streaming kernels as the single-session path. Greedy decode (serving
-agents at temperature 0); graphs are off (batch membership changes).
+streaming kernels as the single-session path. Graphs are off by default
+(batch membership changes).
+
+Every session carries its own sampling parameters (temperature, top_k,
+top_p, seed) and its own count of tokens drawn (``Session.sampled``). A
+batch whose sessions are all at temperature 0 decodes greedily with
+``argmax``, exactly as before sampling existed; otherwise all rows go
+through ``ops.sample_rows`` (`k_sample_filtered_rows`), which reads every
+parameter per row and whose noise depends only on the session's own (seed,
+sampled) — so a session's tokens do not depend on who else is in the batch
+or on its row index, sampled or not.
 """
 
 from __future__ import annotations
@@ -38,7 +47,7 @@ import logging
 import math
 import os as _os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, NamedTuple, Optional, Union
 
 logger = logging.getLogger(__name__)
 
@@ -63,6 +72,54 @@ class Session:
     # every finished turn its emitted tokens (EOS included) and the
     # extension that followed
     context_ids: List[int] = field(default_factory=list)
+    # sampling parameters (ops.sample_filtered semantics; temperature 0 is
+    # greedy) and the number of tokens drawn so far over ALL turns: the
+    # sampler's `step` for the next draw. Monotone, so noise is never reused
+    # across turns; turn 0 numbers its draws like engine.generate().
+    temperature: float = 0.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+    sampled: int = 0
+
+
+class _Draw(NamedTuple):
+    """One row's sampling parameters and step, as the sampler reads them."""
+    temperature: float
+    top_k: int
+    top_p: float
+    seed: int
+    step: int
+
+
+_GREEDY = _Draw(0.0, 0, 1.0, 0, 0)
+
+
+def _check_sampling(temperature, top_k, top_p, seed) -> None:
+    """ValueError unless the values are ones the sampler accepts."""
+    if isinstance(temperature, bool) or \
+            not isinstance(temperature, (int, float)) or \
+            not (0.0 <= temperature < float("inf")):
+        raise ValueError(f"temperature must be a number >= 0, got "
+                         f"{temperature!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or \
+            not 0 <= top_k < 2 ** 31:
+        raise ValueError(f"top_k must be an int >= 0, got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or \
+            not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or \
+            not 0 <= seed < 2 ** 63:
+        raise ValueError(f"seed must be an int in [0, 2^63), got {seed!r}")
+
+
+def _per_item(value, n: int, name: str) -> list:
+    """A scalar applied to all n items, or one entry per item."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name}: {len(value)} entries for {n} items")
+        return list(value)
+    return [value] * n
 
 
 class PagedSessionManager:
@@ -98,6 +155,49 @@ class PagedSessionManager:
         self._graphs: Dict[tuple, dict] = {}
         self.use_graph = m.device.type == "cuda" and \
             _os.environ.get("FEI_SESS_GRAPH", "0") == "1"
+        # True once any session has asked for temperature > 0: from then on
+        # captured steps contain the per-row sampler (greedy rows ride along
+        # at temperature 0). An all-greedy manager never sets it.
+        self._seen_sampled = False
+
+    # -- token selection -------------------------------------------------------
+
+    def _draw_bufs(self, draws: List[_Draw]) -> dict:
+        """The per-row sampler's device state for ``draws``."""
+        dev, B = self.model.device, len(draws)
+        return {
+            "top_k": torch.tensor([d.top_k for d in draws],
+                                  dtype=torch.int32, device=dev),
+            "top_p": torch.tensor([d.top_p for d in draws],
+                                  dtype=torch.float32, device=dev),
+            "temperature": torch.tensor([d.temperature for d in draws],
+                                        dtype=torch.float32, device=dev),
+            "seed": torch.tensor([d.seed for d in draws],
+                                 dtype=torch.int64, device=dev),
+            "step": torch.tensor([d.step for d in draws],
+                                 dtype=torch.int32, device=dev),
+            "token": torch.zeros(B, dtype=torch.int32, device=dev),
+            "info": torch.zeros(B, 2, dtype=torch.float32, device=dev),
+        }
+
+    @staticmethod
+    def _sample_rows(logits: torch.Tensor, bufs: dict) -> torch.Tensor:
+        """One ops.sample_rows draw per logits row into bufs["token"] (which
+        is returned); bufs["step"] is left for the caller to advance."""
+        return ops.sample_rows(
+            logits.contiguous(), bufs["token"], bufs["step"], bufs["info"],
+            top_k=bufs["top_k"], top_p=bufs["top_p"],
+            temperature=bufs["temperature"], seed=bufs["seed"])
+
+    def _select(self, logits: torch.Tensor, draws: List[_Draw]
+                ) -> torch.Tensor:
+        """Next token of every logits row ([B] on the device), row i drawn
+        with draws[i]. All rows greedy: the argmax this manager has always
+        run. Otherwise one per-row sampler launch over all rows."""
+        if all(d.temperature == 0 for d in draws):
+            return logits.argmax(dim=-1)
+        self._seen_sampled = True
+        return self._sample_rows(logits, self._draw_bufs(draws))
 
     def _splits(self, B: int) -> int:
         # batch-aware split count (engine ctor note): the B-wide grid
@@ -120,10 +220,15 @@ class PagedSessionManager:
                             device=m.device))
         return self._ws[B]
 
-    def _chunk_graph(self, B: int, max_blocks: int, token, pos, table):
+    def _chunk_graph(self, B: int, max_blocks: int, token, pos, table,
+                     draws: Optional[List[_Draw]] = None):
         """Capture (or fetch) the hipGraph of ONE decode step for batch B
         and a table of width >= max_blocks: forward + in-place argmax
-        token feedback + pos advance over static buffers. Warm-up runs 2
+        token feedback + pos advance over static buffers. With ``draws``
+        (the manager has seen a sampled session) the token comes from the
+        per-row sampler instead, whose parameter and step tensors are static
+        buffers of the entry too (the capture then also advances step); the
+        two kinds of step are captured under different keys. Warm-up runs 2
         real steps whose KV rows are garbage; they are rewritten by the
         first replays before anything attends them (the per-layer append
         at `pos` precedes the attention read of key `pos`, and rows past
@@ -133,7 +238,7 @@ class PagedSessionManager:
         W = 16
         while W < max_blocks:
             W *= 2
-        key = (B, W)
+        key = (B, W, draws is not None)
         ent = self._graphs.get(key)
         if ent is not None:
             return ent
@@ -144,37 +249,52 @@ class PagedSessionManager:
         bt[:, :max_blocks].copy_(table)
         tk.copy_(token)
         ps.copy_(pos)
+        bufs = self._draw_bufs(draws) if draws is not None else None
+
+        def one_step():
+            lg = self._forward_paged(tk, ps, bt)
+            if bufs is None:
+                tk.copy_(lg.argmax(dim=-1))
+            else:
+                tk.copy_(self._sample_rows(lg, bufs))
+                bufs["step"].add_(1)
+            ps.add_(1)
+
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    lg = self._forward_paged(tk, ps, bt)
-                    tk.copy_(lg.argmax(dim=-1))
-                    ps.add_(1)
+                    one_step()
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                lg = self._forward_paged(tk, ps, bt)
-                tk.copy_(lg.argmax(dim=-1))
-                ps.add_(1)
+                one_step()
             torch.cuda.synchronize()
         except Exception as e:                      # pragma: no cover - GPU
             logger.warning("sessions graph capture failed (%s); "
                            "falling back to eager chunks", e)
             self.use_graph = False
             return None
-        ent = {"graph": g, "token": tk, "pos": ps, "table": bt}
+        ent = {"graph": g, "token": tk, "pos": ps, "table": bt,
+               "draw": bufs}
         self._graphs[key] = ent
-        logger.info("sessions decode step captured (B=%d, W=%d)", B, W)
+        logger.info("sessions decode step captured (B=%d, W=%d, %s)", B, W,
+                    "greedy" if bufs is None else "per-row sampler")
         return ent
 
     # -- admission -----------------------------------------------------------
 
     def open(self, prompt: Union[str, List[int]],
-             max_new_tokens: int = 256) -> int:
-        """Prefill a new session into the pool; returns its id. Raises
-        MemoryError when the pool has no blocks (caller evicts/queues)."""
+             max_new_tokens: int = 256, temperature: float = 0.0,
+             top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> int:
+        """Prefill a new session into the pool; returns its id. The session
+        draws its tokens with (temperature, top_k, top_p, seed) —
+        ops.sample_filtered semantics, temperature 0 is greedy. Raises
+        ValueError for parameters the sampler does not accept (nothing is
+        reserved) and MemoryError when the pool has no blocks (caller
+        evicts/queues)."""
+        _check_sampling(temperature, top_k, top_p, seed)
         ids = (self.engine.tokenizer.encode(prompt)
                if isinstance(prompt, str) else list(prompt))
         S = len(ids)
@@ -185,13 +305,39 @@ class PagedSessionManager:
             self.pool.release(sid)
             raise
         logits = self._prefill_paged(sid, ids, 0)
-        first = int(logits[0].argmax())
+        draw = _Draw(float(temperature), top_k, float(top_p), seed, 0)
+        first = self._first_token(logits, draw)
         sess = Session(sid=sid, prompt_ids=ids, generated=[first], pos=S,
-                       max_new_tokens=max_new_tokens, context_ids=list(ids))
+                       max_new_tokens=max_new_tokens, context_ids=list(ids),
+                       temperature=draw.temperature, top_k=top_k,
+                       top_p=draw.top_p, seed=seed, sampled=1)
         if first == self.eos:
             sess.done = True
         self.sessions[sid] = sess
         return sid
+
+    def _first_token(self, logits: torch.Tensor, draw: _Draw) -> int:
+        """The first token of a turn from its prefill logits [1, vocab]."""
+        if draw.temperature == 0:
+            return int(logits[0].argmax())
+        return int(self._select(logits[:1], [draw])[0])
+
+    def _resolve(self, s: Session, temperature, top_k, top_p, seed) -> _Draw:
+        """extend()'s sampling arguments (None keeps the session's value),
+        validated, with the session's next step."""
+        d = _Draw(s.temperature if temperature is None else temperature,
+                  s.top_k if top_k is None else top_k,
+                  s.top_p if top_p is None else top_p,
+                  s.seed if seed is None else seed, s.sampled)
+        _check_sampling(d.temperature, d.top_k, d.top_p, d.seed)
+        return d._replace(temperature=float(d.temperature),
+                          top_p=float(d.top_p))
+
+    @staticmethod
+    def _start_turn(s: Session, draw: _Draw) -> None:
+        s.temperature, s.top_k = draw.temperature, draw.top_k
+        s.top_p, s.seed = draw.top_p, draw.seed
+        s.sampled += 1                      # the turn's first token
 
     def _prefill_paged(self, sid: int, ids: List[int],
                        pos0: int) -> torch.Tensor:
@@ -212,10 +358,15 @@ class PagedSessionManager:
         return logits
 
     def extend(self, sid: int, prompt: Union[str, List[int]],
-               max_new_tokens: int = 256) -> int:
+               max_new_tokens: int = 256, temperature: Optional[float] = None,
+               top_k: Optional[int] = None, top_p: Optional[float] = None,
+               seed: Optional[int] = None) -> int:
         """Continue a FINISHED session with new prompt tokens (a tool
         result, the next user message); returns the first token of the new
-        turn (greedy). The conversation so far is not prefilled again.
+        turn. The conversation so far is not prefilled again. A sampling
+        parameter left at None keeps the session's value; the session's
+        draw count carries on, so a turn never reuses an earlier turn's
+        noise.
 
         The pool holds KV rows for prompt + generated[:-1] and ``pos``
         counts them: the last emitted token has no row yet. So the prefill
@@ -226,12 +377,14 @@ class PagedSessionManager:
         step writes row p before it attends [0, p].
 
         Raises KeyError (unknown session), ValueError (the session is still
-        active, or pos + 1 + len(new) + max_new_tokens exceeds the model's
-        max_seq_len) and MemoryError (no blocks; the session, its block
-        list and the free list are left exactly as they were)."""
+        active, a sampling parameter is out of range, or pos + 1 + len(new)
+        + max_new_tokens exceeds the model's max_seq_len) and MemoryError
+        (no blocks); after any of them the session, its block list and the
+        free list are exactly as they were."""
         s = self.sessions[sid]                      # KeyError: unknown
         if not s.done:
             raise ValueError(f"session {sid} is still active")
+        draw = self._resolve(s, temperature, top_k, top_p, seed)
         new_ids = (self.engine.tokenizer.encode(prompt)
                    if isinstance(prompt, str) else list(prompt))
         n = 1 + len(new_ids)
@@ -249,12 +402,13 @@ class PagedSessionManager:
             t.length = length
             raise
         logits = self._prefill_paged(sid, [s.generated[-1]] + new_ids, s.pos)
-        first = int(logits[0].argmax())
+        first = self._first_token(logits, draw)
         s.context_ids = s.context_ids + self._emitted(s) + new_ids
         s.pos += n
         s.generated = [first]
         s.max_new_tokens = max_new_tokens
         s.turn += 1
+        self._start_turn(s, draw)
         s.done = first == self.eos
         return first
 
@@ -277,12 +431,15 @@ class PagedSessionManager:
         return True
 
     def open_many(self, prompts, max_new_tokens: int = 256,
-                  max_batch_tokens: Optional[int] = None) -> List[int]:
+                  max_batch_tokens: Optional[int] = None,
+                  temperature=0.0, top_k=0, top_p=1.0, seed=0) -> List[int]:
         """open() for several prompts at once; returns their session ids in
         order. The prompts share packed ragged prefill forwards
         (LlamaModel.forward_prefill_paged_ragged) instead of paying one
         forward each; see _prefill_many for the schedule. Every session ends
-        up exactly as open() would leave it.
+        up exactly as open() would leave it. Each sampling parameter is a
+        scalar for all prompts or a list with one entry per prompt; a bad
+        value or list length raises ValueError before anything is reserved.
 
         All or nothing: blocks for every prompt are reserved first, and when
         the pool runs out MemoryError is raised with the sessions, every
@@ -290,6 +447,14 @@ class PagedSessionManager:
         all_ids = [self._ids(p) for p in prompts]
         if any(not ids for ids in all_ids):
             raise ValueError("open_many: empty prompt")
+        n = len(all_ids)
+        draws = []
+        for t, k, p, sd in zip(_per_item(temperature, n, "temperature"),
+                               _per_item(top_k, n, "top_k"),
+                               _per_item(top_p, n, "top_p"),
+                               _per_item(seed, n, "seed")):
+            _check_sampling(t, k, p, sd)
+            draws.append(_Draw(float(t), k, float(p), sd, 0))
         if not all_ids:
             return []
         sids: List[int] = []
@@ -308,31 +473,46 @@ class PagedSessionManager:
             raise
         if not self._ragged_admission():
             rollback()                          # open() takes the same blocks
-            return [self.open(ids, max_new_tokens) for ids in all_ids]
+            return [self.open(ids, max_new_tokens, d.temperature, d.top_k,
+                              d.top_p, d.seed)
+                    for ids, d in zip(all_ids, draws)]
         firsts = self._prefill_many(
             [(sid, ids, 0) for sid, ids in zip(sids, all_ids)],
-            max_batch_tokens)
-        for sid, ids, first in zip(sids, all_ids, firsts):
+            max_batch_tokens, draws)
+        for sid, ids, first, d in zip(sids, all_ids, firsts, draws):
             self.sessions[sid] = Session(
                 sid=sid, prompt_ids=ids, generated=[first], pos=len(ids),
                 max_new_tokens=max_new_tokens, done=first == self.eos,
-                context_ids=list(ids))
+                context_ids=list(ids), temperature=d.temperature,
+                top_k=d.top_k, top_p=d.top_p, seed=d.seed, sampled=1)
         return sids
 
     def extend_many(self, items, max_new_tokens: int = 256,
-                    max_batch_tokens: Optional[int] = None) -> List[int]:
+                    max_batch_tokens: Optional[int] = None,
+                    temperature=None, top_k=None, top_p=None,
+                    seed=None) -> List[int]:
         """extend() for several finished sessions at once: ``items`` are
         (sid, prompt) pairs; returns the first token of every new turn, in
-        order. The extensions share packed ragged prefill forwards.
+        order. The extensions share packed ragged prefill forwards. Each
+        sampling parameter is None (every session keeps its value), a scalar
+        for all items, or a list with one entry (a value or None) per item.
 
         Everything is validated before anything is touched, with extend()'s
-        errors (KeyError unknown session; ValueError still active, or the
+        errors (KeyError unknown session; ValueError still active, a sampling
+        parameter out of range or a list of the wrong length, or the
         context would exceed max_seq_len) and ValueError for a session that
         appears twice. Then all or nothing: MemoryError leaves every session,
         block list, length and the free list exactly as before the call."""
+        items = list(items)
+        n_items = len(items)
+        per = list(zip(_per_item(temperature, n_items, "temperature"),
+                       _per_item(top_k, n_items, "top_k"),
+                       _per_item(top_p, n_items, "top_p"),
+                       _per_item(seed, n_items, "seed")))
         todo = []
+        draws = []
         seen = set()
-        for sid, prompt in items:
+        for (sid, prompt), given in zip(items, per):
             s = self.sessions[sid]                  # KeyError: unknown
             if sid in seen:
                 raise ValueError(f"session {sid} appears twice")
@@ -346,6 +526,7 @@ class PagedSessionManager:
                     f"session {sid}: context {s.pos} + {n} new + "
                     f"{max_new_tokens} to generate exceeds max_seq_len "
                     f"{self.model.max_seq_len}")
+            draws.append(self._resolve(s, *given))
             todo.append((s, new_ids))
         if not todo:
             return []
@@ -366,24 +547,29 @@ class PagedSessionManager:
             raise
         if not self._ragged_admission():
             rollback()                              # extend() grows them again
-            return [self.extend(s.sid, new_ids, max_new_tokens)
-                    for s, new_ids in todo]
+            return [self.extend(s.sid, new_ids, max_new_tokens,
+                                d.temperature, d.top_k, d.top_p, d.seed)
+                    for (s, new_ids), d in zip(todo, draws)]
         firsts = self._prefill_many(
             [(s.sid, [s.generated[-1]] + new_ids, s.pos)
-             for s, new_ids in todo], max_batch_tokens)
-        for (s, new_ids), first in zip(todo, firsts):
+             for s, new_ids in todo], max_batch_tokens, draws)
+        for (s, new_ids), first, d in zip(todo, firsts, draws):
             s.context_ids = s.context_ids + self._emitted(s) + new_ids
             s.pos += 1 + len(new_ids)
             s.generated = [first]
             s.max_new_tokens = max_new_tokens
             s.turn += 1
             s.done = first == self.eos
+            self._start_turn(s, d)
         return firsts
 
-    def _prefill_many(self, work, max_batch_tokens: Optional[int]
-                      ) -> List[int]:
+    def _prefill_many(self, work, max_batch_tokens: Optional[int],
+                      draws: Optional[List[_Draw]] = None) -> List[int]:
         """Prefill ``work`` = [(sid, ids, pos0)] into blocks already
-        reserved; returns every item's first token (greedy).
+        reserved; returns every item's first token, item i drawn with
+        draws[i] (greedy without ``draws``). A forward whose finished items
+        are all greedy takes the argmax of its logits as it always did; one
+        that finishes a sampled item samples its finished rows only.
 
         Schedule: each item is cut into the pieces _prefill_paged would cut
         it into (LocalEngine.PREFILL_CHUNK tokens from its own start). A
@@ -393,8 +579,10 @@ class PagedSessionManager:
         attends the rows its predecessor writes; an item's later pieces go
         into later forwards with pos0 advanced. A forward always takes at
         least one piece, so a budget below the piece size degrades to one
-        piece per forward. One host sync per forward (the argmax download),
+        piece per forward. One host sync per forward (the token download),
         and only in forwards that finish an item."""
+        if draws is None:
+            draws = [_GREEDY] * len(work)
         m, dev = self.model, self.model.device
         chunk = self.engine.PREFILL_CHUNK
         budget = chunk if max_batch_tokens is None else int(max_batch_tokens)
@@ -433,10 +621,19 @@ class PagedSessionManager:
                 done_at[i] += n
                 if done_at[i] == len(work[i][1]):
                     finished.append((row, i))
-            if finished:
+            if finished and all(draws[i].temperature == 0
+                                for _, i in finished):
                 top = logits.argmax(dim=-1).tolist()        # the one sync
                 for row, i in finished:
                     firsts[i] = int(top[row])
+            elif finished:
+                rows = torch.tensor([row for row, _ in finished],
+                                    dtype=torch.int64, device=dev)
+                top = self._select(logits.index_select(0, rows),
+                                   [draws[i] for _, i in finished]
+                                   ).tolist()               # the one sync
+                for (_, i), t in zip(finished, top):
+                    firsts[i] = int(t)
         return firsts
 
     def _emitted(self, s: Session) -> List[int]:
@@ -457,12 +654,13 @@ class PagedSessionManager:
         return [s for s in self.sessions.values() if not s.done]
 
     def step(self) -> int:
-        """One greedy decode step for every active session. Returns the
-        number of sessions that advanced."""
+        """One decode step for every active session. Returns the number of
+        sessions that advanced."""
         return self.step_chunk(1)
 
     def step_chunk(self, chunk: int = 8) -> int:
-        """Up to ``chunk`` greedy decode steps for the CURRENT active set
+        """Up to ``chunk`` decode steps for the CURRENT active set (every
+        session drawing with its own sampling parameters and draw count)
         with device-resident token feedback — ONE host sync (the chunk's
         token download) instead of one per step; block capacity for the
         whole chunk is reserved up front and the table tensor is built
@@ -470,7 +668,8 @@ class PagedSessionManager:
         hits EOS mid-chunk keeps decoding garbage rows into its reserved
         blocks until the chunk ends (its `generated`/`pos` stop at the
         EOS, so the extra rows are never attended and the blocks are
-        freed on close). Returns sessions advanced (0 = none active)."""
+        freed on close), and keeps drawing; its ``sampled`` advances only by
+        the tokens it keeps. Returns sessions advanced (0 = none active)."""
         act = self.active
         if not act:
             return 0
@@ -490,11 +689,22 @@ class PagedSessionManager:
         token = torch.tensor([s.generated[-1] for s in act],
                              dtype=torch.int64, device=dev)
         pos = torch.tensor([s.pos for s in act], dtype=torch.int32, device=dev)
-        g = self._chunk_graph(len(act), max_blocks, token, pos, table) \
+        draws = [_Draw(s.temperature, s.top_k, s.top_p, s.seed, s.sampled)
+                 for s in act]
+        greedy = all(d.temperature == 0 for d in draws)
+        # a manager that has served a sampled session keeps ONE kind of
+        # captured step (the sampler; greedy rows ride along at T = 0)
+        g = self._chunk_graph(
+            len(act), max_blocks, token, pos, table,
+            draws if self._seen_sampled else None) \
             if self.use_graph else None
         if g is not None:
             g["token"].copy_(token)
             g["pos"].copy_(pos)
+            if g["draw"] is not None:
+                fresh = self._draw_bufs(draws)
+                for name in ("top_k", "top_p", "temperature", "seed", "step"):
+                    g["draw"][name].copy_(fresh[name])
             g["table"].zero_()
             g["table"][:, :max_blocks].copy_(table)
             outs = torch.empty(len(act), chunk, dtype=torch.int64,
@@ -504,10 +714,15 @@ class PagedSessionManager:
                 outs[:, j].copy_(g["token"])
             allt = outs.tolist()                           # the one sync
         else:
+            bufs = None if greedy else self._draw_bufs(draws)
             steps = []
             for _ in range(chunk):
                 logits = self._forward_paged(token, pos, table)
-                token = logits.argmax(dim=-1)
+                if bufs is None:
+                    token = logits.argmax(dim=-1)
+                else:
+                    token = self._sample_rows(logits, bufs).to(torch.int64)
+                    bufs["step"].add_(1)
                 steps.append(token)
                 pos = pos + 1
             allt = torch.stack(steps, dim=1).tolist()      # the one sync
@@ -515,6 +730,7 @@ class PagedSessionManager:
             for t in allt[i]:
                 s.generated.append(int(t))
                 s.pos += 1
+                s.sampled += 1
                 if int(t) == self.eos or \
                         len(s.generated) >= s.max_new_tokens:
                     s.done = True
@@ -535,7 +751,11 @@ class PagedSessionManager:
         return {"token_ids": gen,
                 "text": self.engine.tokenizer.decode(gen),
                 "done": s.done,
-                "turn": s.turn}
+                "turn": s.turn,
+                "temperature": s.temperature,
+                "top_k": s.top_k,
+                "top_p": s.top_p,
+                "seed": s.seed}
 
     # -- model forward over the pool ------------------------------------------
 

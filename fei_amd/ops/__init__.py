@@ -66,6 +66,9 @@ def _try_load() -> None:
     lib.fei_sample_shard.argtypes = [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _vp]
     lib.fei_sample_filtered.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                         _f, _f, _u64, _i, _vp]
+    lib.fei_sample_filtered_rows.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _i, _i, _vp]
+    lib.fei_sample_filtered_rows.restype = _i
     lib.fei_rope_kv8_decode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _i, _i, _i, _i, _i, _l, _l,
                                         _vp]
@@ -670,6 +673,70 @@ def sample_filtered(logits: torch.Tensor, token: torch.Tensor,
     lib.fei_sample_filtered(_ptr(logits), _ptr(token), out_ptr, _ptr(step),
                             _ptr(info), B, V, int(top_k), float(top_p),
                             float(temperature), int(seed), max_new, _stream())
+    return token
+
+
+def _check_rows_arg(name: str, t, dtype: torch.dtype, shape, device) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got "
+                         f"{tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on {device}, got {t.device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def sample_rows(logits: torch.Tensor, token: torch.Tensor,
+                step: torch.Tensor, info: torch.Tensor, *,
+                top_k: torch.Tensor, top_p: torch.Tensor,
+                temperature: torch.Tensor, seed: torch.Tensor) -> torch.Tensor:
+    """sample_filtered() with every parameter per row, for continuous
+    batching: row b of ``logits`` [B,V] is drawn with top_k[b] (i32),
+    top_p[b] (f32), temperature[b] (f32), seed[b] (i64) and step[b] (i32),
+    all device tensors of length B. ``token`` [B] i32 and ``info`` [B,2] f32
+    are written; ``step`` is not (the caller advances it with step.add_(1)).
+
+    Row b's token and info equal sample_filtered() on logits[b:b+1] alone
+    with that row's scalars, wherever the row sits in the batch (the noise
+    does not depend on the row index). Nothing is a kernel argument except
+    the sizes, so the call is hipGraph-capturable and a captured launch
+    follows in-place parameter changes. Argument dtype / shape / device /
+    contiguity errors raise ValueError naming the argument; parameter VALUES
+    are not checked here (that would need a sync)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError("logits must be a [B, V] tensor")
+    if not logits.is_contiguous():
+        raise ValueError("logits must be contiguous")
+    if logits.is_cuda and logits.dtype != torch.bfloat16:
+        raise ValueError(f"logits must be bfloat16 on the GPU, got "
+                         f"{logits.dtype}")
+    B, V = logits.shape
+    dev = logits.device
+    _check_rows_arg("token", token, torch.int32, (B,), dev)
+    _check_rows_arg("step", step, torch.int32, (B,), dev)
+    _check_rows_arg("info", info, torch.float32, (B, 2), dev)
+    _check_rows_arg("top_k", top_k, torch.int32, (B,), dev)
+    _check_rows_arg("top_p", top_p, torch.float32, (B,), dev)
+    _check_rows_arg("temperature", temperature, torch.float32, (B,), dev)
+    _check_rows_arg("seed", seed, torch.int64, (B,), dev)
+    if not logits.is_cuda:
+        for b in range(B):
+            sample_filtered(logits[b:b + 1], token[b:b + 1], step[b:b + 1],
+                            info[b:b + 1], temperature=float(temperature[b]),
+                            seed=int(seed[b]), top_k=int(top_k[b]),
+                            top_p=float(top_p[b]))
+        return token
+    lib = require_lib()
+    rc = lib.fei_sample_filtered_rows(
+        _ptr(logits), _ptr(token), _ptr(info), _ptr(top_k), _ptr(top_p),
+        _ptr(temperature), _ptr(seed), _ptr(step), B, V, _stream())
+    if rc != 0:
+        raise ValueError(f"sample_rows: empty batch or vocabulary "
+                         f"(B={B}, V={V})")
     return token
 
 

@@ -4,14 +4,20 @@ POST /v1/completions        prompt, max_tokens, temperature, top_k, top_p,
                             stop, n, stream (SSE), echo+logprobs (eval),
                             speculative, cache_prefix
 POST /v1/chat/completions   messages=[{role, content}], ... (+ stream SSE)
-POST /v1/sessions           open a paged continuous-batching session
+POST /v1/sessions           open a paged continuous-batching session:
+                            prompt, max_tokens, temperature, top_k, top_p,
+                            seed (per session; defaults are greedy)
 POST /v1/sessions/batch     open several sessions in shared ragged prefill
-                            forwards (prompts=[...]); all or nothing
+                            forwards (prompts=[...]); all or nothing. The
+                            sampling fields are scalars for all prompts or
+                            lists with one entry per prompt
 POST /v1/sessions/step      advance all sessions (?n=K); reports the pool's
                             free_blocks and kv_dtype ("fp8" when the engine
                             was created with kv_quant="fp8")
-GET  /v1/sessions/{id}      poll result     DELETE /v1/sessions/{id}  close
-POST /v1/sessions/{id}/extend   continue a finished session (next turn)
+GET  /v1/sessions/{id}      poll result (echoes the sampling parameters)
+DELETE /v1/sessions/{id}    close
+POST /v1/sessions/{id}/extend   continue a finished session (next turn);
+                            a sampling field left out keeps the session's
 GET  /v1/models             available ModelSpecs
 GET  /health                engine + device status
 
@@ -26,7 +32,7 @@ from __future__ import annotations
 
 import threading
 import time
-from typing import List, Optional
+from typing import List, Optional, Union
 
 from pydantic import BaseModel
 
@@ -59,16 +65,30 @@ class ChatMessage(BaseModel):
 class SessionOpen(BaseModel):
     prompt: str
     max_tokens: int = 256
+    temperature: float = 0.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
 
 
 class SessionOpenBatch(BaseModel):
     prompts: List[str]
     max_tokens: int = 256
+    # one value for all prompts, or one per prompt
+    temperature: Union[float, List[float]] = 0.0
+    top_k: Union[int, List[int]] = 0
+    top_p: Union[float, List[float]] = 1.0
+    seed: Union[int, List[int]] = 0
 
 
 class SessionExtend(BaseModel):
     prompt: str
     max_tokens: int = 256
+    # None keeps the session's value
+    temperature: Optional[float] = None
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    seed: Optional[int] = None
 
 
 class ChatRequest(BaseModel):
@@ -288,7 +308,12 @@ def create_app(engine: Optional[LocalEngine] = None,
         from fastapi import HTTPException
         with lock:
             try:
-                sid = _mgr().open(req.prompt, max_new_tokens=req.max_tokens)
+                sid = _mgr().open(req.prompt, max_new_tokens=req.max_tokens,
+                                  temperature=req.temperature,
+                                  top_k=req.top_k, top_p=req.top_p,
+                                  seed=req.seed)
+            except ValueError as e:          # bad sampling parameter
+                raise HTTPException(status_code=400, detail=str(e))
             except MemoryError as e:
                 raise HTTPException(status_code=503, detail=str(e))
         return {"session_id": sid}
@@ -296,15 +321,19 @@ def create_app(engine: Optional[LocalEngine] = None,
     @app.post("/v1/sessions/batch")
     def session_open_batch(req: SessionOpenBatch):
         """Open several sessions in shared ragged prefill forwards
-        (PagedSessionManager.open_many): 400 on an empty list or an empty
-        prompt, 503 on pool exhaustion with NOTHING admitted."""
+        (PagedSessionManager.open_many): 400 on an empty list, an empty
+        prompt, a bad sampling parameter or a parameter list whose length is
+        not len(prompts); 503 on pool exhaustion. NOTHING is admitted then."""
         from fastapi import HTTPException
         if not req.prompts:
             raise HTTPException(status_code=400, detail="prompts is empty")
         with lock:
             try:
                 sids = _mgr().open_many(req.prompts,
-                                        max_new_tokens=req.max_tokens)
+                                        max_new_tokens=req.max_tokens,
+                                        temperature=req.temperature,
+                                        top_k=req.top_k, top_p=req.top_p,
+                                        seed=req.seed)
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
             except MemoryError as e:
@@ -335,7 +364,8 @@ def create_app(engine: Optional[LocalEngine] = None,
     def session_extend(sid: int, req: SessionExtend):
         """Continue a finished session with new prompt tokens (the next
         turn): 404 unknown session, 409 still decoding, 400 context
-        overflow, 503 pool exhausted (the session is left untouched)."""
+        overflow or a bad sampling parameter, 503 pool exhausted (the
+        session is left untouched)."""
         from fastapi import HTTPException
         with lock:
             mgr = _mgr()
@@ -346,8 +376,11 @@ def create_app(engine: Optional[LocalEngine] = None,
                                     detail="session is still active")
             try:
                 first = mgr.extend(sid, req.prompt,
-                                   max_new_tokens=req.max_tokens)
-            except ValueError as e:          # context overflow
+                                   max_new_tokens=req.max_tokens,
+                                   temperature=req.temperature,
+                                   top_k=req.top_k, top_p=req.top_p,
+                                   seed=req.seed)
+            except ValueError as e:          # context overflow, bad parameter
                 raise HTTPException(status_code=400, detail=str(e))
             except MemoryError as e:
                 raise HTTPException(status_code=503, detail=str(e))
