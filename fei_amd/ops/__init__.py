@@ -139,6 +139,14 @@ def _try_load() -> None:
         fn.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i,
                        _vp]
         fn.restype = _i
+    for fn in (lib.fei_gemv_addnorm_ring, lib.fei_gemv_swiglu_addnorm_ring):
+        fn.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i,
+                       _i, _vp]
+        fn.restype = _i
+    lib.fei_gemv_addnorm_ring_slots.argtypes = [_i, _i, _i, _i]
+    lib.fei_gemv_addnorm_ring_slots.restype = _i
+    lib.fei_gemv_addnorm_ring_max_trips.argtypes = []
+    lib.fei_gemv_addnorm_ring_max_trips.restype = _i
     lib.fei_gemv_deep.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
     lib.fei_gemv_deep.restype = _i
     _LIB = lib
@@ -1062,13 +1070,109 @@ def gemv_swiglu_norm(res: torch.Tensor, wnorm: torch.Tensor,
 
 # -- residual add + RMSNorm folded into the consuming GEMV -------------------
 
+# The ring schedule (K <= 4096): a wave refills each weight slot with the
+# next row group's as soon as it has been dotted, and groups are dealt
+# grid-stride. FEI_ADDNORM_RING=0 restores the drain-between-groups kernels
+# with contiguous groups, 2 per workgroup unless a count is forced.
+_ADDNORM_RING = os.environ.get("FEI_ADDNORM_RING", "1") != "0"
+
 # Row groups one workgroup walks behind a single add+norm prologue (a group
 # is 8 rows in gemv_addnorm, 4 in gemv_swiglu_addnorm). Pure scheduling: a
-# row's sum does not depend on which workgroup owns it.
-# FEI_ADDNORM_RG / FEI_ADDNORM_RG_SWIGLU override (profiles/gemv_addnorm.md).
-_ADDNORM_ROW_GROUPS = max(1, int(os.environ.get("FEI_ADDNORM_RG", "2") or 2))
-_ADDNORM_ROW_GROUPS_SWIGLU = max(
-    1, int(os.environ.get("FEI_ADDNORM_RG_SWIGLU", "2") or 2))
+# row's sum does not depend on which workgroup owns it. 0 = automatic: one
+# resident round of workgroups covers every group (_addnorm_plan); measured
+# behind the fixed counts below at 8B, so opt-in.
+# FEI_ADDNORM_RG / FEI_ADDNORM_RG_SWIGLU override
+# (profiles/gemv_addnorm.md, profiles/gemv_addnorm_ring.md).
+_ADDNORM_DRAIN_RG = 2
+_ADDNORM_RG_DEFAULT = 2
+_ADDNORM_RG_SWIGLU_DEFAULT = 5 if _ADDNORM_RING else _ADDNORM_DRAIN_RG
+_ADDNORM_ROW_GROUPS = max(0, int(
+    os.environ.get("FEI_ADDNORM_RG", "") or _ADDNORM_RG_DEFAULT))
+_ADDNORM_ROW_GROUPS_SWIGLU = max(0, int(
+    os.environ.get("FEI_ADDNORM_RG_SWIGLU", "") or _ADDNORM_RG_SWIGLU_DEFAULT))
+
+_ADDNORM_RING_MAX_K = 4096           # the preload holds the whole row slice
+_ADDNORM_RING_MAX_TRIPS = 8          # kernel instances, one per trip count
+
+
+def _addnorm_plan(groups: int, slots: int,
+                  max_trips: int = _ADDNORM_RING_MAX_TRIPS) -> Tuple[int, int]:
+    """(grid, trips) of the automatic rule: min(groups, slots) workgroups,
+    each walking group = block + g * grid for g < trips, so trip counts are
+    at most one apart. More than max_trips * slots groups need further
+    rounds: the grid then grows past `slots` at max_trips."""
+    if groups < 1 or slots < 1:
+        raise ValueError("groups and slots must be positive")
+    grid = min(groups, slots)
+    trips = -(-groups // grid)
+    if trips > max_trips:
+        trips = max_trips
+        grid = -(-groups // trips)
+    return grid, trips
+
+
+def _addnorm_fixed_plan(groups: int, rg: int) -> Tuple[int, int]:
+    """(grid, trips) for a forced count of groups per workgroup."""
+    return -(-groups // rg), rg
+
+
+_ADDNORM_SLOTS: dict = {}
+_ADDNORM_PLANS: dict = {}
+
+
+def _addnorm_slots(swiglu: bool, nt: int, trips: int, K: int) -> int:
+    """Workgroups of one ring kernel instance the device holds at once (the
+    occupancy query, once per instance and K)."""
+    key = (bool(swiglu), int(nt), int(trips), int(K),
+           torch.cuda.current_device())
+    slots = _ADDNORM_SLOTS.get(key)
+    if slots is None:
+        slots = require_lib().fei_gemv_addnorm_ring_slots(
+            int(swiglu), int(nt), int(trips), int(K))
+        if slots < 1:
+            raise RuntimeError(
+                f"fei_gemv_addnorm_ring_slots failed (rc={slots})")
+        _ADDNORM_SLOTS[key] = slots
+    return slots
+
+
+def _addnorm_auto_plan(swiglu: bool, nt: int, K: int,
+                       groups: int) -> Tuple[int, int]:
+    """The automatic plan on this device. An instance's slots depend on its
+    trip count and the trip count on the slots: take the smallest trip count
+    whose own instance covers every group in one round."""
+    key = (bool(swiglu), int(nt), int(K), int(groups),
+           torch.cuda.current_device())
+    plan = _ADDNORM_PLANS.get(key)
+    if plan is None:
+        for t in range(1, _ADDNORM_RING_MAX_TRIPS + 1):
+            plan = _addnorm_plan(groups, _addnorm_slots(swiglu, nt, t, K))
+            if plan[1] <= t:
+                break
+        _ADDNORM_PLANS[key] = plan
+    return plan
+
+
+def _addnorm_launch(swiglu: bool, rg: int, out, delta, res_in, res_out, wnorm,
+                    w, M: int, N: int, K: int, eps: float, nt: int) -> None:
+    lib = require_lib()
+    name = "fei_gemv_swiglu_addnorm" if swiglu else "fei_gemv_addnorm"
+    ptrs = (_ptr(out), _ptr(delta), _ptr(res_in), _ptr(res_out), _ptr(wnorm),
+            _ptr(w))
+    if (_ADDNORM_RING and K <= _ADDNORM_RING_MAX_K
+            and rg <= _ADDNORM_RING_MAX_TRIPS):
+        groups = -(-N // (4 if swiglu else 8))
+        grid, trips = (_addnorm_fixed_plan(groups, rg) if rg >= 1 else
+                       _addnorm_auto_plan(swiglu, nt, K, groups))
+        name += "_ring"
+        rc = getattr(lib, name)(*ptrs, M, N, K, eps, nt, grid, trips,
+                                _stream())
+    else:
+        rc = getattr(lib, name)(*ptrs, M, N, K, eps, nt,
+                                rg if rg >= 1 else _ADDNORM_DRAIN_RG,
+                                _stream())
+    if rc != 0:
+        raise RuntimeError(f"{name} refused the launch (rc={rc})")
 
 
 def _addnorm_ok(M: int, K: int) -> bool:
@@ -1116,11 +1220,8 @@ def gemv_addnorm(delta: torch.Tensor, res_in: torch.Tensor,
         out = torch.empty(*res_in.shape[:-1], N, dtype=res_in.dtype,
                           device=res_in.device)
     nt = 1 if (N * K * 2 >= _GEMV_NT_MIN_BYTES) else 0
-    rc = lib.fei_gemv_addnorm(_ptr(out), _ptr(d2), _ptr(res_in),
-                              _ptr(res_out), _ptr(wnorm), _ptr(w), M, N, K,
-                              eps, nt, _ADDNORM_ROW_GROUPS, _stream())
-    if rc != 0:
-        raise RuntimeError(f"fei_gemv_addnorm refused the launch (rc={rc})")
+    _addnorm_launch(False, _ADDNORM_ROW_GROUPS, out, d2, res_in, res_out,
+                    wnorm, w, M, N, K, eps, nt)
     return out
 
 
@@ -1146,13 +1247,8 @@ def gemv_swiglu_addnorm(delta: torch.Tensor, res_in: torch.Tensor,
         out = torch.empty(*res_in.shape[:-1], I, dtype=res_in.dtype,
                           device=res_in.device)
     nt = 1 if (wgu.shape[0] * K * 2 >= _GEMV_NT_MIN_BYTES) else 0
-    rc = lib.fei_gemv_swiglu_addnorm(_ptr(out), _ptr(d2), _ptr(res_in),
-                                     _ptr(res_out), _ptr(wnorm), _ptr(wgu),
-                                     M, I, K, eps, nt,
-                                     _ADDNORM_ROW_GROUPS_SWIGLU, _stream())
-    if rc != 0:
-        raise RuntimeError(
-            f"fei_gemv_swiglu_addnorm refused the launch (rc={rc})")
+    _addnorm_launch(True, _ADDNORM_ROW_GROUPS_SWIGLU, out, d2, res_in,
+                    res_out, wnorm, wgu, M, I, K, eps, nt)
     return out
 
 
