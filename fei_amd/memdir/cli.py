@@ -42,7 +42,19 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="bm25 FTS index instead of the grammar scan "
                         "(build: memdir index)")
 
-    sub.add_parser("index", help="(re)build the lexical FTS index")
+    p.add_argument("--semantic", action="store_true",
+                   help="embedding-index top-k instead of the grammar scan "
+                        "(build: memdir index --semantic)")
+    p.add_argument("--folder", default=None,
+                   help="with --semantic: restrict to one folder")
+    p.add_argument("--status", default=None,
+                   help="with --semantic: restrict to one status")
+    p.add_argument("--topk", type=int, default=10,
+                   help="with --semantic: results to return")
+
+    p = sub.add_parser("index", help="(re)build the lexical FTS index")
+    p.add_argument("--semantic", action="store_true",
+                   help="build the embedding index instead")
 
     p = sub.add_parser("flag", help="set flags on a memory")
     p.add_argument("memory_id")
@@ -91,7 +103,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         print("moved" if ok else "failed")
         return 0 if ok else 1
     if args.cmd == "search":
-        if args.fts:
+        if args.fts and args.semantic:
+            parser.error("--fts and --semantic exclude each other")
+        if args.semantic:
+            from fei_amd.memdir.embed_index import EmbeddingIndex
+            results = EmbeddingIndex(base=base).search_memories(
+                " ".join(args.query), topk=args.topk,
+                folders=None if args.folder is None else [args.folder],
+                statuses=None if args.status is None else [args.status])
+        elif args.fts:
             from fei_amd.memdir.fts_index import FtsIndex
             results = FtsIndex(base=base).search_memories(" ".join(args.query))
         else:
@@ -99,6 +119,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         print(msearch.format_results(results, args.format))
         return 0
     if args.cmd == "index":
+        if args.semantic:
+            from fei_amd.memdir.embed_index import EmbeddingIndex
+            print(f"indexed {EmbeddingIndex(base=base).build()} memories")
+            return 0
         from fei_amd.memdir.fts_index import FtsIndex
         n = FtsIndex(base=base).build()
         print(f"indexed {n} memories")

@@ -149,6 +149,9 @@ def _try_load() -> None:
     lib.fei_gemv_addnorm_ring_max_trips.restype = _i
     lib.fei_gemv_deep.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
     lib.fei_gemv_deep.restype = _i
+    lib.fei_score_topk.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _i, _i, _i, _i, _i, _i, _i, _vp]
+    lib.fei_score_topk.restype = _i
     _LIB = lib
 
 
@@ -1921,3 +1924,126 @@ def gemv_swiglu_norm_fp8(res, wnorm, w8, wscale, eps: float = 1e-5,
     lib.fei_gemv_swiglu_norm_fp8(_ptr(out), _ptr(r2), _ptr(wnorm), _ptr(w8),
                                  _ptr(wscale), M, I, K, eps, _stream())
     return out
+
+
+# -- fused score + top-k over an embedding corpus (csrc/score_topk.hip) ------
+
+SCORE_TOPK_MAX_K = 64
+SCORE_TOPK_MAX_Q = 8
+SCORE_TOPK_MAX_C = 2048
+SCORE_TOPK_MAX_WG = 65536
+# Corpus bytes past which the scan loads nontemporal: a corpus that fits the
+# 256 MiB L3 is worth keeping there between queries, a larger one only
+# evicts everything else (k_gemv's rule, with the threshold this op needs
+# because a corpus, unlike a decode step's weights, can be small).
+_SCORE_TOPK_NT_MIN_BYTES = int(os.environ.get("FEI_SCORE_TOPK_NT_MIN",
+                                              256 << 20))
+# Scan workgroups per CU: 4 up to four queries, 2 beyond (at Q = 8 the
+# per-wave top-k warm-up and the 226-register instance favour fewer, longer
+# slabs: 1.15 vs 1.33 ms at 1M x 768; profiles/score_topk.md).
+_SCORE_TOPK_WG_PER_CU = 4
+_SCORE_TOPK_WG_PER_CU_WIDE = 2
+
+
+def _score_topk_check(emb, q, k, mask, workgroups) -> Tuple[int, int, int]:
+    """Argument checks of score_topk, the same on CPU and GPU; returns
+    (N, C, Q) with q seen as [Q, C]."""
+    name = "score_topk"
+    if not isinstance(emb, torch.Tensor) or emb.dim() != 2:
+        raise ValueError(f"{name}: emb must be a [N, C] tensor")
+    if emb.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{name}: emb must be float32 or float16, got "
+                         f"{emb.dtype}")
+    N, C = emb.shape
+    if not isinstance(q, torch.Tensor) or q.dim() not in (1, 2):
+        raise ValueError(f"{name}: q must be a [C] or [Q, C] tensor")
+    if q.dtype != torch.float32:
+        raise ValueError(f"{name}: q must be float32, got {q.dtype}")
+    Q = 1 if q.dim() == 1 else q.shape[0]
+    if q.shape[-1] != C:
+        raise ValueError(f"{name}: q has {q.shape[-1]} columns, emb has {C}")
+    if q.device != emb.device:
+        raise ValueError(f"{name}: q lives on {q.device}, emb on "
+                         f"{emb.device}")
+    if isinstance(k, bool) or not isinstance(k, int) \
+            or not 1 <= k <= SCORE_TOPK_MAX_K:
+        raise ValueError(f"{name}: k must be an int in 1.."
+                         f"{SCORE_TOPK_MAX_K}, got {k!r}")
+    if not 1 <= Q <= SCORE_TOPK_MAX_Q:
+        raise ValueError(f"{name}: 1..{SCORE_TOPK_MAX_Q} queries per call, "
+                         f"got {Q}")
+    if C < 8 or C % 8 != 0 or C > SCORE_TOPK_MAX_C:
+        raise ValueError(f"{name}: C must be a multiple of 8 in 8.."
+                         f"{SCORE_TOPK_MAX_C}, got {C}")
+    if not 1 <= N < 2 ** 31:
+        raise ValueError(f"{name}: N must be in 1..2^31-1, got {N}")
+    if not emb.is_contiguous():
+        raise ValueError(f"{name}: emb must be contiguous (row stride C)")
+    if not q.is_contiguous():
+        raise ValueError(f"{name}: q must be contiguous")
+    if emb.data_ptr() % 16 or q.data_ptr() % 16:
+        raise ValueError(f"{name}: emb and q must be 16-byte aligned")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8:
+            raise ValueError(f"{name}: mask must be a uint8 tensor")
+        if tuple(mask.shape) != (N,):
+            raise ValueError(f"{name}: mask must have shape ({N},), got "
+                             f"{tuple(mask.shape)}")
+        if mask.device != emb.device:
+            raise ValueError(f"{name}: mask lives on {mask.device}, emb on "
+                             f"{emb.device}")
+        if not mask.is_contiguous():
+            raise ValueError(f"{name}: mask must be contiguous")
+    if workgroups is not None:
+        if isinstance(workgroups, bool) or not isinstance(workgroups, int) \
+                or not 1 <= workgroups <= SCORE_TOPK_MAX_WG:
+            raise ValueError(f"{name}: workgroups must be an int in 1.."
+                             f"{SCORE_TOPK_MAX_WG}, got {workgroups!r}")
+    return N, C, Q
+
+
+def score_topk(emb: torch.Tensor, q: torch.Tensor, k: int,
+               mask: Optional[torch.Tensor] = None, *,
+               workgroups: Optional[int] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best rows of emb [N, C] (f32 or f16) for each query of q [Q, C]
+    (f32, Q <= 8) by dot product: (scores f32 [Q, k], rows int32 [Q, k]),
+    sorted by (score descending, row ascending). q may be [C]; the result is
+    then [k]. ``mask``: uint8 [N], non-zero = eligible; ineligible rows are
+    skipped inside the scan, not filtered afterwards, and are never read.
+    With fewer than k eligible rows the tail is (-inf, -1).
+
+    GPU: one pass of k_score_topk_partial over the corpus plus
+    k_score_topk_final (csrc/score_topk.hip); the score vector is never
+    materialised. ``workgroups`` overrides the scan's grid (tests: the
+    result does not depend on it); the default is a few workgroups per CU,
+    clamped so each has rows. CPU: reference.score_topk. Shapes, dtypes,
+    limits (k <= 64, C % 8 == 0, C <= 2048), contiguity and alignment are
+    checked first: ValueError, nothing launched."""
+    N, C, Q = _score_topk_check(emb, q, k, mask, workgroups)
+    q2 = q.view(Q, C)
+    if not emb.is_cuda:
+        s, i = ref.score_topk(emb, q2, k, mask)
+    else:
+        lib = require_lib()
+        if workgroups is None:
+            per_cu = _SCORE_TOPK_WG_PER_CU if Q <= 4 \
+                else _SCORE_TOPK_WG_PER_CU_WIDE
+            workgroups = per_cu * _cu_count(emb.device)
+        WG = max(1, min(workgroups, N))
+        dev = emb.device
+        part_s = torch.empty(Q, WG, k, dtype=torch.float32, device=dev)
+        part_i = torch.empty(Q, WG, k, dtype=torch.int32, device=dev)
+        s = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        i = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        nt = 1 if N * C * emb.element_size() > _SCORE_TOPK_NT_MIN_BYTES else 0
+        rc = lib.fei_score_topk(
+            _ptr(emb), _ptr(q2), _ptr(mask) if mask is not None else None,
+            _ptr(part_s), _ptr(part_i), _ptr(s), _ptr(i), N, C, Q, k, WG,
+            1 if emb.dtype == torch.float16 else 0, nt, _stream())
+        if rc != 0:
+            raise ValueError(f"score_topk: the kernel refused N={N} C={C} "
+                             f"Q={Q} k={k} workgroups={WG} (code {rc})")
+    if q.dim() == 1:
+        return s[0], i[0]
+    return s, i

@@ -16,7 +16,7 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfei_kernels.s
 SOURCES = ["fei_kernels.hip", "attn_prefill.hip", "gemv.hip", "attn_decode_fused.hip", "gemv_fp8.hip", "stream_layer.hip",
            "sample_filtered.hip", "kv_fp8.hip", "gemv_addnorm.hip",
            "attn_prefill_paged.hip", "kv_fp8_paged.hip",
-           "attn_prefill_ragged.hip", "sample_rows.hip"]
+           "attn_prefill_ragged.hip", "sample_rows.hip", "score_topk.hip"]
 HEADERS = ["fei_common.h", "kv_fp8_common.h", "sample_filtered_body.h"]
 HIPCC = os.environ.get("HIPCC", "hipcc")
 ARCH = os.environ.get("FEI_AMD_ARCH", "gfx950")

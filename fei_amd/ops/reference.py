@@ -373,3 +373,34 @@ def hash_gumbel(B: int, v_local: int, v_offset: int, seed: int,
             out[b] = (m + 1.0) * (1.0 / 16777216.0)
     u = torch.from_numpy(out)
     return -torch.log(-torch.log(u))
+
+
+def score_topk(emb: torch.Tensor, q: torch.Tensor, k: int,
+               mask: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best eligible rows of emb [N, C] per query of q [Q, C]:
+    (scores f32 [Q, k], rows int32 [Q, k]). Scores are
+    ``emb.float() @ q.float().T``; rows are taken in the total order (score
+    descending, then row ascending), which torch.topk does not promise on
+    ties. ``mask`` [N]: non-zero rows are eligible (None: all). A NaN score
+    counts as -inf. With fewer than k eligible rows the tail is (-inf, -1)."""
+    N = emb.shape[0]
+    Q = q.shape[0]
+    scores = (emb.float() @ q.float().t()).t().contiguous()      # [Q, N]
+    scores = torch.nan_to_num(scores, nan=float("-inf"),
+                              posinf=float("inf"), neginf=float("-inf"))
+    elig = torch.ones(N, dtype=torch.bool) if mask is None else mask != 0
+    rows = torch.nonzero(elig).flatten()
+    out_s = torch.full((Q, k), float("-inf"), dtype=torch.float32)
+    out_i = torch.full((Q, k), -1, dtype=torch.int32)
+    n = min(k, rows.numel())
+    if n == 0:
+        return out_s, out_i
+    for u in range(Q):
+        s = scores[u, rows]
+        # stable sort of rows already in ascending order: ties keep the
+        # lower row first
+        order = torch.sort(s, descending=True, stable=True).indices[:n]
+        out_s[u, :n] = s[order]
+        out_i[u, :n] = rows[order].to(torch.int32)
+    return out_s, out_i

@@ -45,15 +45,21 @@ MEMORY_SEARCH_TOOL = {
 MEMORY_SEMANTIC_SEARCH_TOOL = {
     "name": "memory_semantic_search",
     "description": ("Semantic search over memories via the GPU embedding "
-                    "index (cosine top-k). Build the index first with "
-                    "memory_index_build."),
+                    "index (cosine top-k). folder / status restrict the "
+                    "search before selection; queries (a list) searches "
+                    "several texts in one corpus scan and returns one result "
+                    "list per query. query is required unless queries is "
+                    "given. Build the index first with memory_index_build."),
     "input_schema": {
         "type": "object",
         "properties": {
             "query": {"type": "string"},
+            "queries": {"type": "array", "items": {"type": "string"},
+                        "description": "Several queries, one scan"},
             "topk": {"type": "integer"},
+            "folder": {"type": "string", "description": "Restrict to one folder"},
+            "status": {"type": "string", "enum": ["cur", "new", "tmp"]},
         },
-        "required": ["query"],
     },
 }
 
@@ -186,9 +192,23 @@ class MemoryTools:
         return {"count": len(results), "results": results[:limit]}
 
     def semantic_search(self, args: Dict[str, Any]) -> Dict[str, Any]:
-        results = self.index().search_memories(args["query"],
-                                               topk=args.get("topk", 10))
-        if not results and self.index().embeddings is None:
+        index = self.index()
+        topk = args.get("topk", 10)
+        folders = [args["folder"]] if args.get("folder") is not None else None
+        statuses = [args["status"]] if args.get("status") else None
+        queries = args.get("queries")
+        if queries is None and "query" not in args:
+            return {"error": "query is required when queries is absent"}
+        if queries is not None:
+            hits = index.search_many(list(queries), topk, folders, statuses)
+            if index.embeddings is None:
+                return {"error": "no semantic index; run memory_index_build first"}
+            per_query = [index._resolve(h, True) for h in hits]
+            return {"count": sum(len(r) for r in per_query),
+                    "queries": list(queries), "results": per_query}
+        results = index.search_memories(args["query"], topk=topk,
+                                        folders=folders, statuses=statuses)
+        if not results and index.embeddings is None:
             return {"error": "no semantic index; run memory_index_build first"}
         return {"count": len(results), "results": results}
 
@@ -360,9 +380,15 @@ class MemoryManager:
         return self.save_memory(subject, body="\n".join(lines), tags=tags)
 
     def recall(self, query: str, semantic: bool = False,
-               topk: int = 10) -> List[Dict[str, Any]]:
+               topk: int = 10, folder: Optional[str] = None,
+               status: Optional[str] = None) -> List[Dict[str, Any]]:
+        args: Dict[str, Any] = {"query": query}
+        if folder is not None:
+            args["folder"] = folder
+        if status is not None:
+            args["status"] = status
         if semantic:
-            return self.tools.semantic_search({"query": query, "topk": topk}) \
+            return self.tools.semantic_search({**args, "topk": topk}) \
                 .get("results", [])
-        return self.tools.search({"query": query, "with_content": True}) \
+        return self.tools.search({**args, "with_content": True}) \
             .get("results", [])
