@@ -48,7 +48,8 @@ def _try_load() -> None:
     lib.fei_attn_decode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp,
                                     _i, _i, _i, _i, _i, _i, _f, _l,
                                     _vp, _vp, _vp, _l, _vp, _vp, _i, _vp]
-    lib.fei_attn_decode_combine.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
+    lib.fei_attn_decode_combine.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                            _vp]
     lib.fei_swiglu.argtypes = [_vp, _vp, _l, _i, _vp]
     lib.fei_sample.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64,
                                _i, _vp]
@@ -62,7 +63,7 @@ def _try_load() -> None:
                                           _vp, _i, _i, _i, _i, _i, _f,
                                           _l, _l, _vp]
     lib.fei_sample_onepass.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _f, _u64,
-                                       _i, _vp]
+                                       _i, _i, _vp]
     lib.fei_sample_shard.argtypes = [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _vp]
     lib.fei_sample_filtered.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                         _f, _f, _u64, _i, _vp]
@@ -432,7 +433,33 @@ def attn_decode(q, k_cache, v_cache, pos, splits: int = 32,
                         layer, _stream())
     if arrive is None:
         lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
-                                    B, Hq, D, splits, _stream())
+                                    B, Hq, D, splits, int(_CMB_FLAT),
+                                    _stream())
+    return out
+
+
+def attn_decode_combine(part_o: torch.Tensor, part_ml: torch.Tensor,
+                        out: Optional[torch.Tensor] = None,
+                        flat: Optional[bool] = None) -> torch.Tensor:
+    """The split-K combine of decode attention on its own: part_o
+    [B,Hq,splits,D] f32 and part_ml [B,Hq,splits,2] f32 (m, l) as the
+    attention kernels write them -> out [B,Hq,D] bf16. `flat` as in
+    sample(): None follows FEI_CMB_FLAT."""
+    lib = require_lib()
+    B, Hq, splits, D = part_o.shape
+    assert part_o.dtype == torch.float32 and part_o.is_contiguous()
+    assert part_ml.dtype == torch.float32 and part_ml.is_contiguous()
+    assert part_ml.shape == (B, Hq, splits, 2)
+    assert D in (64, 128), f"decode attention supports D in (64,128), got {D}"
+    assert 1 <= splits <= 64, "combine kernel stages at most 64 split partials"
+    if out is None:
+        out = torch.empty(B, Hq, D, dtype=torch.bfloat16,
+                          device=part_o.device)
+    assert out.shape == (B, Hq, D) and out.is_contiguous()
+    lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
+                                B, Hq, D, splits,
+                                int(_CMB_FLAT if flat is None else flat),
+                                _stream())
     return out
 
 
@@ -473,7 +500,7 @@ def _attn_decode_kv8(lib, q, k_cache, v_cache, pos, splits, scale, workspace,
     if rc != 0:
         raise RuntimeError(f"fei_attn_decode_kv8 refused the launch (rc={rc})")
     lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
-                                B, Hq, D, splits, _stream())
+                                B, Hq, D, splits, int(_CMB_FLAT), _stream())
     return out
 
 
@@ -615,10 +642,13 @@ def sample(logits: torch.Tensor, token: torch.Tensor,
            step: torch.Tensor, workspace: torch.Tensor,
            out_tokens: Optional[torch.Tensor] = None,
            temperature: float = 0.0, seed: int = 0,
-           nchunks: int = 64) -> torch.Tensor:
+           nchunks: int = 64, flat: Optional[bool] = None) -> torch.Tensor:
     """Greedy (T<=0) or Gumbel-max categorical (T>0) sampling.
     logits [B,V] bf16 -> token [B] int32 (written in place; also appended to
-    out_tokens[b, step] when given). All state on device (hipGraph-safe)."""
+    out_tokens[b, step] when given). All state on device (hipGraph-safe).
+    `flat` picks the one-pass kernel at B <= 8: the preloading one (True,
+    rows up to 131072 wide) or the looping one (False); None follows
+    FEI_SAMPLE_FLAT. Same token either way."""
     B, V = logits.shape
     if not logits.is_cuda:
         if temperature <= 0:
@@ -642,7 +672,9 @@ def sample(logits: torch.Tensor, token: torch.Tensor,
     out_ptr = _ptr(out_tokens) if out_tokens is not None else None
     if B <= 8:
         lib.fei_sample_onepass(_ptr(logits), _ptr(token), out_ptr, _ptr(step),
-                               B, V, temperature, seed, max_new, _stream())
+                               B, V, temperature, seed, max_new,
+                               int(_SAMPLE_FLAT if flat is None else flat),
+                               _stream())
     else:
         lib.fei_sample(_ptr(logits), _ptr(token), out_ptr, _ptr(step),
                        _ptr(workspace), B, V, nchunks, temperature, seed,
@@ -872,6 +904,15 @@ _GEMV_NT_MIN_BYTES = int(os.environ.get("FEI_GEMV_NT_MIN", 0))
 # 4-protocol measurement ladder is profiles/r02_fused_combine.md).
 # Opt-in via FEI_FUSED_CMB=1; the launch form stays the default.
 _FUSED_CMB = os.environ.get("FEI_FUSED_CMB", "0") == "1"
+# Split-K combine and one-pass sampler with every load issued before the
+# first wait (k_attn_decode_combine_flat at 16 and 32 splits,
+# k_sample_onepass_flat up to vocab 131072), bit-identical to the looping
+# kernels they replace. Both read what other XCDs have just written, so each
+# dependent load was a full trip to memory. FEI_CMB_FLAT=0 / FEI_SAMPLE_FLAT=0
+# restore the looping kernels for A/B inside one build
+# (profiles/combine_sample_flat.md).
+_CMB_FLAT = os.environ.get("FEI_CMB_FLAT", "1") != "0"
+_SAMPLE_FLAT = os.environ.get("FEI_SAMPLE_FLAT", "1") != "0"
 # Batch-1 plain decode chain: run the residual add + RMSNorm in front of the
 # gate/up and qkv GEMVs as those GEMVs' prologue (gemv_addnorm /
 # gemv_swiglu_addnorm, bit-identical to the launches they replace) instead
@@ -1340,7 +1381,7 @@ def attn_decode_paged(q, k_pool, v_pool, block_table, pos, splits: int = 32,
                               block_table.shape[1], splits, scale,
                               q.stride(0), kin, vin, cs, kv_bs, _stream())
     lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
-                                B, Hq, D, splits, _stream())
+                                B, Hq, D, splits, int(_CMB_FLAT), _stream())
     return out
 
 
@@ -1466,7 +1507,7 @@ def _attn_decode_paged_kv8(q, k_pool, v_pool, block_table, pos, splits, scale,
         raise RuntimeError(
             f"fei_attn_decode_paged_kv8 refused the launch (rc={rc})")
     lib.fei_attn_decode_combine(_ptr(out), _ptr(part_o), _ptr(part_ml),
-                                B, Hq, D, splits, _stream())
+                                B, Hq, D, splits, int(_CMB_FLAT), _stream())
     return out
 
 

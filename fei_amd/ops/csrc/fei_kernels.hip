@@ -886,9 +886,101 @@ __global__ void k_attn_decode_combine(u16* __restrict__ out,
   out[((long)b * Hq + hq) * D + d] = f2bf(l > 0.f ? o / l : 0.f);
 }
 
+}  // extern "C"
+
+// Flat combine: the split count is a template parameter, so every load the
+// workgroup needs is written out and issued before the first wait. The
+// partials were just written by other XCDs' attention workgroups, so each
+// load is a full trip past the local L2; k_attn_decode_combine above pays
+// one such trip for m/l and one more per 8 splits (hipcc unrolls its quad
+// loop by two and drains vmcnt at the end of every pass: 5 trips at 32
+// splits), this kernel pays one. The m/l loads go first: memory returns in
+// order, so the staging write waits for them alone (vmcnt(SPLITS)) and the
+// o partials land behind the barrier. Same expressions in the same order
+// as the kernel above — results are bit-identical
+// (profiles/combine_sample_flat.md). D is a template parameter too, so a
+// load's address is one uniform base plus the lane's offset and an immediate
+// instead of a 64-bit VGPR pair per split.
+template <int SPLITS, int D>
+__global__ void __launch_bounds__(D)
+k_attn_decode_combine_flat(u16* __restrict__ out,
+                           const float* __restrict__ part_o,
+                           const float* __restrict__ part_ml, int Hq) {
+  constexpr int NML = (2 * SPLITS + 63) / 64;     // staging loads per thread
+  static_assert(NML * D >= 2 * SPLITS, "the staging loads cover all of m/l");
+  const int hq = blockIdx.x;
+  const int b = blockIdx.y;
+  const unsigned d = threadIdx.x;
+  // NML * D >= 2 * SPLITS slots: every thread stages what it loaded, so
+  // the m/l load sits in no branch the compiler could sink it into
+  __shared__ float sml[NML * D / 2][2];
+  const float* pml = part_ml + ((long)b * Hq + hq) * SPLITS * 2;
+  const float* po = part_o + ((long)b * Hq + hq) * SPLITS * D;
+  float ml[NML];
+#pragma unroll
+  for (int k = 0; k < NML; ++k) {
+    const unsigned i = d + k * D;
+    ml[k] = pml[i < 2 * SPLITS ? i : 0u];         // clamped, never past m/l
+  }
+  __builtin_amdgcn_sched_barrier(0);              // m/l first: it is waited first
+  float ov[SPLITS];
+#pragma unroll
+  for (int s = 0; s < SPLITS; ++s) ov[s] = (po + s * D)[d];
+  // every load above is issued before anything below is scheduled
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < NML; ++k) {
+    ((float*)sml)[d + k * D] = ml[k];
+  }
+  __syncthreads();
+  float m = -1.0f / 0.0f;
+#pragma unroll
+  for (int s = 0; s < SPLITS; ++s) m = fmaxf(m, sml[s][0]);
+  float l = 0.f, o = 0.f;
+#pragma unroll
+  for (int s = 0; s + 4 <= SPLITS; s += 4) {
+    const float o0 = ov[s + 0];
+    const float o1 = ov[s + 1];
+    const float o2 = ov[s + 2];
+    const float o3 = ov[s + 3];
+    const float w0 = __expf(sml[s + 0][0] - m);
+    const float w1 = __expf(sml[s + 1][0] - m);
+    const float w2 = __expf(sml[s + 2][0] - m);
+    const float w3 = __expf(sml[s + 3][0] - m);
+    l += w0 * sml[s + 0][1] + w1 * sml[s + 1][1] +
+         w2 * sml[s + 2][1] + w3 * sml[s + 3][1];
+    o += w0 * o0 + w1 * o1 + w2 * o2 + w3 * o3;
+  }
+  static_assert(SPLITS % 4 == 0, "whole quads only: no per-split tail");
+  out[((long)b * Hq + hq) * D + d] = f2bf(l > 0.f ? o / l : 0.f);
+}
+
+extern "C" {
+
+// flat != 0 takes k_attn_decode_combine_flat at the split counts the decode
+// paths dispatch (32, and 16 at batch >= 4), the two it was measured at;
+// every other count, and flat == 0, the kernel above.
 void fei_attn_decode_combine(void* out, const float* part_o,
                              const float* part_ml, int B, int Hq, int D,
-                             int splits, hipStream_t stream) {
+                             int splits, int flat, hipStream_t stream) {
+#define LAUNCH_CMB_FLAT(S) do { \
+    if (D == 128) \
+      hipLaunchKernelGGL((k_attn_decode_combine_flat<S, 128>), dim3(Hq, B), \
+                         dim3(128), 0, stream, (u16*)out, part_o, part_ml, \
+                         Hq); \
+    else \
+      hipLaunchKernelGGL((k_attn_decode_combine_flat<S, 64>), dim3(Hq, B), \
+                         dim3(64), 0, stream, (u16*)out, part_o, part_ml, \
+                         Hq); \
+  } while (0)
+  if (flat && (D == 64 || D == 128)) {
+    switch (splits) {
+      case 16: LAUNCH_CMB_FLAT(16); return;
+      case 32: LAUNCH_CMB_FLAT(32); return;
+      default: break;
+    }
+  }
+#undef LAUNCH_CMB_FLAT
   hipLaunchKernelGGL(k_attn_decode_combine, dim3(Hq, B), dim3(D), 0, stream,
                      (u16*)out, part_o, part_ml, B, Hq, D, splits);
 }
@@ -1101,9 +1193,123 @@ k_sample_onepass(const u16* __restrict__ logits, int* __restrict__ token,
   }
 }
 
+}  // extern "C"
+
+// Flat one-pass sampler: a thread issues all DEPTH vec8 loads of its strip
+// before it looks at any of them. The row was just written by the lm_head
+// GEMV's workgroups on other XCDs, so every load is a trip past the local
+// L2; k_sample_onepass above waits for each load before issuing the next
+// (16 trips in a row at vocab 128256), this kernel waits once. Rows with
+// vocab/8 <= 1024*DEPTH only. Slots past the row re-read its last vector
+// (in bounds) and are skipped by the compare loop. GUMBEL hoists the
+// temperature test out of the element loop; the arithmetic, the visiting
+// order, the tie-break and everything after the loops are the kernel
+// above's, and so is the token (profiles/combine_sample_flat.md).
+template <int DEPTH, bool GUMBEL>
+__global__ void __launch_bounds__(1024)
+k_sample_onepass_flat(const u16* __restrict__ logits, int* __restrict__ token,
+                      int* __restrict__ out_tokens,
+                      const int* __restrict__ step, int B, int vocab,
+                      float temperature, u64 seed, int max_new) {
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const s16x8* row = (const s16x8*)(logits + (long)b * vocab);
+  const int nv = vocab >> 3;                      // >= 1 (host checks)
+  s16x8 buf[DEPTH];
+#pragma unroll
+  for (int k = 0; k < DEPTH; ++k) {
+    const int i = tid + k * 1024;
+    buf[k] = row[i < nv ? i : nv - 1];
+  }
+  // every load above is issued before anything below is scheduled
+  __builtin_amdgcn_sched_barrier(0);
+  const u64 st = (u64)(*step);
+  const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
+  float best = -1.0f / 0.0f;
+  int besti = 0x7fffffff;
+#pragma unroll
+  for (int k = 0; k < DEPTH; ++k) {
+    const int i = tid + k * 1024;
+    const bool live = i < nv;
+    const s16x8 v8 = buf[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int idx = i * 8 + j;
+      float v = bf2f((u16)v8[j]) * invT;
+      if (GUMBEL) {
+        float u = hash_uniform(seed ^ (st * 0x51ed27f1ull) ^ ((u64)b << 40) ^ (u64)idx);
+        // the kernel above multiplies and adds in separate basic blocks,
+        // so its product is rounded before the add: no fma here either
+        asm volatile("" : "+v"(v));
+        v += -__logf(-__logf(u));
+      }
+      // selects, not branches: a branch on `live` lets hipcc sink that
+      // slot's load into it, behind the other slots' waits
+      const bool take = live & ((v > best) | ((v == best) & (idx < besti)));
+      best = take ? v : best;
+      besti = take ? idx : besti;
+    }
+  }
+  // tail (vocab % 8)
+  for (int idx = nv * 8 + tid; idx < vocab; idx += blockDim.x) {
+    float v = bf2f(logits[(long)b * vocab + idx]) * invT;
+    if (GUMBEL) {
+      float u = hash_uniform(seed ^ (st * 0x51ed27f1ull) ^ ((u64)b << 40) ^ (u64)idx);
+      asm volatile("" : "+v"(v));
+      v += -__logf(-__logf(u));
+    }
+    if (v > best || (v == best && idx < besti)) { best = v; besti = idx; }
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const int oi = __shfl_xor(besti, off);
+    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+  }
+  __shared__ float rv[16];
+  __shared__ int ri[16];
+  const int wid = tid >> 6;
+  if ((tid & 63) == 0) { rv[wid] = best; ri[wid] = besti; }
+  __syncthreads();
+  if (tid == 0) {
+    const int nw = blockDim.x >> 6;
+    for (int i = 1; i < nw; ++i)
+      if (rv[i] > best || (rv[i] == best && ri[i] < besti)) {
+        best = rv[i]; besti = ri[i];
+      }
+    token[b] = besti;
+    if (out_tokens && (int)st < max_new)
+      out_tokens[(long)b * max_new + (int)st] = besti;
+  }
+}
+
+extern "C" {
+
+// flat != 0 takes k_sample_onepass_flat at the smallest preload depth that
+// holds the row; a longer row, and flat == 0, the kernel above.
 void fei_sample_onepass(const void* logits, int* token, int* out_tokens,
                         const int* step, int B, int vocab, float temperature,
-                        u64 seed, int max_new, hipStream_t stream) {
+                        u64 seed, int max_new, int flat,
+                        hipStream_t stream) {
+#define LAUNCH_SAMPLE_FLAT(DEPTH) do { \
+    if (temperature > 0.f) \
+      hipLaunchKernelGGL((k_sample_onepass_flat<DEPTH, true>), dim3(B), \
+                         dim3(1024), 0, stream, (const u16*)logits, token, \
+                         out_tokens, step, B, vocab, temperature, seed, \
+                         max_new); \
+    else \
+      hipLaunchKernelGGL((k_sample_onepass_flat<DEPTH, false>), dim3(B), \
+                         dim3(1024), 0, stream, (const u16*)logits, token, \
+                         out_tokens, step, B, vocab, temperature, seed, \
+                         max_new); \
+  } while (0)
+  const int nv = vocab >> 3;
+  if (flat && nv >= 1) {
+    if (nv <= 1024 * 4) { LAUNCH_SAMPLE_FLAT(4); return; }
+    if (nv <= 1024 * 8) { LAUNCH_SAMPLE_FLAT(8); return; }
+    if (nv <= 1024 * 16) { LAUNCH_SAMPLE_FLAT(16); return; }
+  }
+#undef LAUNCH_SAMPLE_FLAT
   hipLaunchKernelGGL(k_sample_onepass, dim3(B), dim3(1024), 0, stream,
                      (const u16*)logits, token, out_tokens, step, B, vocab,
                      temperature, seed, max_new);
