@@ -17,7 +17,8 @@ SOURCES = ["fei_kernels.hip", "attn_prefill.hip", "gemv.hip", "attn_decode_fused
            "sample_filtered.hip", "kv_fp8.hip", "gemv_addnorm.hip",
            "attn_prefill_paged.hip", "kv_fp8_paged.hip",
            "attn_prefill_ragged.hip", "sample_rows.hip", "score_topk.hip"]
-HEADERS = ["fei_common.h", "kv_fp8_common.h", "sample_filtered_body.h"]
+HEADERS = ["fei_common.h", "kv_fp8_common.h", "sample_filtered_body.h",
+           "attn_prefill_core.h"]
 HIPCC = os.environ.get("HIPCC", "hipcc")
 ARCH = os.environ.get("FEI_AMD_ARCH", "gfx950")
 

@@ -16,8 +16,10 @@
 // (tests/test_prefill_paged_gpu.py): k_attn_prefill_paged<D> keeps
 // k_attn_prefill<D>'s grid, wave -> row ownership, 64-key LDS tiles, both
 // swizzles, zero padding, MFMA chains, online softmax, P reshape and
-// epilogue expression for expression. When one of the two changes, change
-// the other.
+// epilogue expression for expression. That text now lives in
+// attn_prefill_core.h (k_attn_prefill and the ragged kernel are built on it);
+// this kernel keeps its own copy because on the core it measured slower
+// (profiles/prefill_core.md). When the core changes, change this copy.
 #include "fei_common.h"
 
 namespace {

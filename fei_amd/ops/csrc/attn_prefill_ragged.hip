@@ -24,13 +24,12 @@
 // Bit identity with the uniform paged kernels is the contract
 // (tests/test_prefill_ragged_gpu.py): per sequence the rows are bit-equal to
 // k_rope_kv_prefill_paged / k_attn_prefill_paged<D> run with B = 1 on that
-// sequence alone. k_attn_prefill_paged_ragged<D> IS k_attn_prefill_paged<D>
-// with S := len_b and the q/out base := cu[b]: wave -> row ownership, 64-key
-// LDS tiles, both swizzles, the table stage one tile ahead, zero padding,
-// MFMA chains, online softmax, P reshape and epilogue are kept expression
-// for expression. When one of the two changes, change the other
-// (attn_prefill_paged.hip, and through it attn_prefill.hip).
-#include "fei_common.h"
+// sequence alone. k_attn_prefill_paged_ragged<D> is k_attn_prefill_paged<D>
+// with S := len_b and the q/out base := cu[b]; its tiles, swizzles, table
+// stage, MFMA chains, softmax and epilogue are the shared tile core
+// (attn_prefill_core.h), of which k_attn_prefill_paged<D> keeps a copy. When
+// the core or the staging loop below changes, change attn_prefill_paged.hip.
+#include "attn_prefill_core.h"
 
 namespace {
 
@@ -79,8 +78,10 @@ __global__ void k_rope_kv_prefill_paged_ragged(
 // ---------------------------------------------------------------------------
 // Causal GQA prefill attention over the pool for a packed batch. grid
 // (n_tiles, Hq), block 256 = 4 waves; tile_map[2*i] = sequence, [2*i+1] = q
-// tile of work item i. See attn_prefill_paged.hip for the table stage and
-// attn_prefill.hip for the structure and fragment maps.
+// tile of work item i. Tiles, table stage, compute and epilogue are the tile
+// core's (attn_prefill_core.h); the slot fetch is k_attn_prefill_paged's.
+// The staging loop runs one trip at a time, as the compiler leaves
+// k_attn_prefill's.
 //
 // Resources: as k_attn_prefill_paged<D> (40 KB + 256 B of LDS at D=128, 3
 // workgroups per CU; 4 at D=64); the sequence's bounds and bases are
@@ -89,7 +90,8 @@ __global__ void k_rope_kv_prefill_paged_ragged(
 // ---------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 4, D == 128 ? 3 : 4)))
+__attribute__((amdgpu_waves_per_eu(prefill::WAVES_PER_SIMD<D>,
+                                   prefill::WAVES_PER_SIMD<D>)))
 k_attn_prefill_paged_ragged(const u16* __restrict__ q,
                             const u16* __restrict__ kp,
                             const u16* __restrict__ vp,
@@ -100,192 +102,52 @@ k_attn_prefill_paged_ragged(const u16* __restrict__ q,
                             const int* __restrict__ tile_map, int Hq, int Hkv,
                             int bs_log, int max_blocks, float scale,
                             long q_ts) {
-  constexpr int DC = D / 16;       // d-chunks (8 for D=128)
-  constexpr int KS = D / 32;       // K-dim steps per QK^T mfma chain
-  constexpr int KV = 64;           // keys per LDS tile (one barrier per 64)
-  constexpr int NC = KV / 16;      // 16-key score chunks per tile
-  constexpr int KA = KV / 32;      // P A-fragments per tile (K=32 each)
-  constexpr int NIT = KV * D / 8 / 256;   // staging trips per thread
+  using namespace prefill;
+  constexpr int NIT = KV * D / 8 / 256;            // staging trips per thread
   const int b = tile_map[2 * blockIdx.x];          // sequence
   const int qt = tile_map[2 * blockIdx.x + 1];     // its 64-row q tile
   const int hq = blockIdx.y;
   const int hkv = hq / (Hq / Hkv);
   const int tid = threadIdx.x;
-  const int w = tid >> 6;          // wave 0..3
-  const int lane = tid & 63;
-  const int l15 = lane & 15;
-  const int lg = lane >> 4;        // 16-lane group 0..3
-  const int tok0 = cu[b];                          // first packed row
-  const int S = cu[b + 1] - tok0;                  // len_b
-
-  // same tiles and swizzles as k_attn_prefill (attn_prefill.hip)
-  __shared__ u16 kt[64][D];
-  __shared__ u16 vtT[D][64];
-  __shared__ u16 p_lds[4][16][64];
-#define SWZ16(row, col8) ((col8) ^ ((row) & 7))
-#define VT_OFF(col, key) \
-  ((col) * 64 + \
-   ((((key) >> 3) ^ ((col) & 7) ^ (((col) >> 3) & 7)) << 3) + ((key) & 7))
-
+  const long tok0 = cu[b];                         // first packed row
+  const int S = cu[b + 1] - (int)tok0;             // len_b
   const int p0 = pos0[b];
-  const int q_hi = min(qt * 64 + 64, S);           // exclusive rel row bound
-  const int kv_end = p0 + q_hi;
-
-  // ---- load Q fragments (row = l&15 within this wave's 16-row block) ----
-  const int qrow_rel = qt * 64 + w * 16 + l15;     // A-fragment row
-  const int qrow_ld = min(qrow_rel, S - 1);        // clamp: own rows only
-  s16x8 a_q[KS];
-  {
-    const u16* qp = q + ((long)tok0 + qrow_ld) * q_ts + (long)hq * D + 8 * lg;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-      a_q[ks] = *(const s16x8*)(qp + ks * 32);
-  }
-
-  // online-softmax state per C row r (replicated across the 16-lane group)
-  float m_row[4], l_row[4];
-  f32x4 o_acc[DC];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m_row[r] = -1.0f / 0.0f; l_row[r] = 0.f; }
-#pragma unroll
-  for (int dc = 0; dc < DC; ++dc) o_acc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+  const int kv_end = p0 + min(qt * 64 + 64, S);    // exclusive key bound
   const int BS = 1 << bs_log;
   const int* bt = block_table + (long)b * max_blocks;
 
-  // physical block of key t*KV + (tid & 63); a key >= kv_end has none (its
-  // table entry is never read, and neither is its bts slot)
+  __shared__ Tiles<D> T;
   __shared__ int bts[KV];
-  int blk_next;
-  auto load_block = [&](int t) {
-    const int kk = t * KV + (tid & 63);
-    blk_next = kk < kv_end ? bt[kk >> bs_log] : 0;
-  };
-  load_block(0);
+  Wave<D> st;
+  wave_init<D>(st, q, tok0, qt, S, hq, q_ts);
+  int blk_next = table_load(bt, 0, kv_end, bs_log);
 
   const int ntiles = (kv_end + KV - 1) / KV;
   for (int t = 0; t < ntiles; ++t) {
     // ---- stage K/V tile (KV keys x D), zero-padded past kv_end ----------
-    if (tid < KV) bts[tid] = blk_next;              // read after the barrier
+    table_publish(bts, blk_next);                   // read after the barrier
     __syncthreads();                                // vt/kt reuse protection
-    {
 #pragma unroll 1
-      for (int it = 0; it < NIT; ++it) {
-        const int i = tid + it * 256;
-        const int key = i / (D / 8);
-        const int col8 = i % (D / 8);
-        const int kk = t * KV + key;
-        const int dst = key * (D / 8) + SWZ16(key, col8);
-        s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        s16x8 v8 = z;
-        if (kk < kv_end) {
-          const long row =
-              (((long)bts[key] * Hkv + hkv) * BS + (kk & (BS - 1))) * D;
-          ((s16x8*)kt)[dst] = *(const s16x8*)(kp + row + col8 * 8);
-          v8 = *(const s16x8*)(vp + row + col8 * 8);
-        } else {
-          ((s16x8*)kt)[dst] = z;
-        }
-        // V transposed scatter (VT_OFF block swizzle)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          ((u16*)vtT)[VT_OFF(col8 * 8 + j, key)] = (u16)v8[j];
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + it * 256;
+      const int key = i / (D / 8);
+      const int col8 = i % (D / 8);
+      const int kk = t * KV + key;
+      s16x8 k8 = {0, 0, 0, 0, 0, 0, 0, 0};
+      s16x8 v8 = k8;
+      if (kk < kv_end) {
+        const long row =
+            (((long)bts[key] * Hkv + hkv) * BS + (kk & (BS - 1))) * D;
+        k8 = *(const s16x8*)(kp + row + col8 * 8);
+        v8 = *(const s16x8*)(vp + row + col8 * 8);
       }
+      store_slot<D>(T, key, col8, k8, v8);
     }
     __syncthreads();
-    load_block(t + 1);             // past the last tile every key >= kv_end
-
-    // ---- QK^T: NC 16-key chunks ---------------------------------------
-    f32x4 sfrag[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int krow = c * 16 + l15;
-        const int kcol8 = SWZ16(krow, ks * 4 + lg);
-        const s16x8 b_k = *(const s16x8*)(&((s16x8*)kt)[krow * (D / 8) + kcol8]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_q[ks], b_k, acc, 0, 0, 0);
-      }
-      sfrag[c] = acc;
-    }
-
-    // ---- mask + online softmax ----------------------------------------
-    float p_val[NC][4];
-    float alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow_abs = p0 + qt * 64 + w * 16 + 4 * lg + r;
-      float sv[NC];
-      float mx = -1.0f / 0.0f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        sv[c] = sfrag[c][r] * scale;
-        const int key = t * KV + c * 16 + l15;
-        if (key >= kv_end || key > qrow_abs) sv[c] = -1.0f / 0.0f;
-        mx = fmaxf(mx, sv[c]);
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-      const float m_new = fmaxf(m_row[r], mx);
-      alpha[r] = __expf(m_row[r] - m_new);          // 0 on first tile
-      m_row[r] = m_new;
-      float psum = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        p_val[c][r] = (sv[c] == -1.0f / 0.0f) ? 0.f : __expf(sv[c] - m_new);
-        psum += p_val[c][r];
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) psum += __shfl_xor(psum, off);
-      l_row[r] = l_row[r] * alpha[r] + psum;
-    }
-
-    // ---- rescale O, stage P (C-layout -> A-layout via LDS) -------------
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o_acc[dc][r] *= alpha[r];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        p_lds[w][4 * lg + r][c * 16 + l15] = f2bf(p_val[c][r]);
-    // same-wave LDS RAW: compiler inserts lgkmcnt waits; no barrier needed
-    // (p_lds[w] is private to wave w).
-
-    // ---- PV: KA P-fragments of K=32 each -------------------------------
-    s16x8 a_p[KA];
-#pragma unroll
-    for (int ka = 0; ka < KA; ++ka)
-      a_p[ka] = *(const s16x8*)(&p_lds[w][l15][ka * 32 + 8 * lg]);
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc) {
-      const int col = dc * 16 + l15;
-#pragma unroll
-      for (int ka = 0; ka < KA; ++ka) {
-        // 8 consecutive keys of this column = one 16-byte read
-        const s16x8 b_v = *(const s16x8*)(
-            &((u16*)vtT)[VT_OFF(col, ka * 32 + 8 * lg)]);
-        o_acc[dc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_p[ka], b_v,
-                                                            o_acc[dc], 0, 0, 0);
-      }
-    }
+    blk_next = table_load(bt, t + 1, kv_end, bs_log);
+    tile_compute<D>(st, T, t, kv_end, p0, qt, scale, 1);
   }
-
-  // ---- epilogue: O / l, store (rows of this sequence only) --------------
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int srow = qt * 64 + w * 16 + 4 * lg + r;
-    if (srow >= S) continue;
-    const float inv_l = l_row[r] > 0.f ? 1.f / l_row[r] : 0.f;
-    u16* orow = out + (((long)tok0 + srow) * Hq + hq) * D;
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc)
-      orow[dc * 16 + l15] = f2bf(o_acc[dc][r] * inv_l);
-  }
-#undef SWZ16
-#undef VT_OFF
+  epilogue<D>(st, out, tok0, qt, S, hq, Hq);
 }
 
 // log2 of a power-of-two block size, -1 for anything else

@@ -307,10 +307,11 @@ k_attn_decode_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
 // scale, rounded to bf16 and written to the same swizzled kt / transposed
 // vtT LDS tiles. QK^T / PV MFMA chains and the softmax are the bf16 kernel's.
 // Slots past kv_end are zero-padded without touching data or scales.
-// Everything below the staging block is a copy of k_attn_prefill (kept
-// separate so the bf16 kernel's code and register figures stay untouched):
-// a fix to the softmax, the swizzles or the epilogue there belongs here too.
-// Fragment maps (attn_prefill.hip header, verified by k_mfma_probe):
+// Everything below the staging block is a copy of the tile core that
+// k_attn_prefill is built on (attn_prefill_core.h), kept because this kernel
+// measured slower on the core (profiles/prefill_core.md): a fix to the
+// softmax, the swizzles or the epilogue there belongs here too.
+// Fragment maps (attn_prefill_core.h header, verified by k_mfma_probe):
 //   A[16x32]: lane l -> A[l&15][8*(l>>4)+j], j=0..7
 //   B[32x16]: lane l -> B[8*(l>>4)+j][l&15]
 //   C[16x16]: lane l, reg r -> C[4*(l>>4)+r][l&15]

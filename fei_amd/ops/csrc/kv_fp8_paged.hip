@@ -287,8 +287,9 @@ k_attn_decode_paged_kv8(const u16* __restrict__ q, u8* __restrict__ kd,
 // drops the registers into bts in front of the next tile's first barrier and
 // the staging loop reads bts[key]. A key >= kv_end has no entry: its table
 // slot is never read, and neither are its bts slot, codes or scales.
-// Everything below the staging block is k_attn_prefill_kv8's (and so
-// k_attn_prefill's): a fix there belongs here too.
+// Everything below the staging block is k_attn_prefill_kv8's, a copy of the
+// tile core (attn_prefill_core.h) kept because this kernel measured slower on
+// the core (profiles/prefill_core.md): a fix there belongs here too.
 // LDS: k_attn_prefill_kv8's + 256 B, which changes no workgroups-per-CU
 // count; the waves-per-SIMD target is the contiguous kernel's.
 // ---------------------------------------------------------------------------
